@@ -20,9 +20,16 @@ frame end"); torch.distributed (gloo, on the CPU) carries only the
 rendezvous, barriers and the timing reductions.  Total work is fixed as N
 grows -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (driver contract), with the roofline of the
-dominant kernel (HIP-event timed inside the timed region) and a CPU baseline
-(the oracle restatement on a bounded row sample, rank 0 at N=1 only).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does what the
+headline needs and no more: set-up, warmup, the timed steps, one untimed
+re-run of the timed frames with device counters (the rays of `value`), and
+the line, whose roofline object carries what the timed launches themselves
+gave (HIP-event kernel time, the PMC record of these sources).  `--full` adds
+what takes runs of its own: the reference walk's work on the timed frames
+(roofline.reference_equivalent, config.node_visits_per_ray / rect_tests_per_ray)
+and the CPU baselines (the oracle restatement on a bounded row sample, rank 0
+at N=1 only).  `--dump-outputs DIR` writes the frame the last timed step
+delivered on rank 0 as DIR/frame.npy (float32).
 """
 from __future__ import annotations
 
@@ -52,6 +59,7 @@ VALU_PEAK_TOPS = 78.6          # 256 CU x 4 SIMD x 32 lanes/cycle x 2.4 GHz, non
 BYTES_PER_RAY = 136            # SoA path state read+write + hit record
 BYTES_PER_PIXEL = 16           # float4 output
 OPS_PER_AABB, OPS_PER_RECT = 25, 71  # SURVEY.md §8(d) VALU model of the reference BVH walk
+DUMP_BYTES_MAX = 64_000_000    # --dump-outputs: all files together
 SRC_GLOBS = ("mirror-maze_amd/csrc/*", "mirror-maze_amd/Makefile", "include/*.h")
 
 
@@ -123,12 +131,41 @@ def parse():
                    help="diagnostics on one GPU: trace only rank 0's row set of an N-rank split")
     p.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                    help="mm_set_option on every context (MM_OPT_* numbers, include/mm_api.h); results never change")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (approx)")
+    p.add_argument("--full", action="store_true",
+                   help="also what takes runs of its own: the reference walk's work on the timed frames "
+                        "(roofline.reference_equivalent, node visits / rect tests per ray) and the CPU baselines")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="rank 0 writes the frame the last timed step delivered as DIR/frame.npy (float32; the "
+                        "RGBA8 frame's bytes as 0..255); a frame above 64 MB as a fixed seeded sample of its rows, "
+                        "their indices in DIR/frame_rows.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (approx; --full)")
     p.add_argument("--src-hash", action="store_true", help="print the product source hash and exit")
     p.add_argument("--save-frame", default="", help="rank 0 saves the last timed frame as it was delivered "
                                                     "(.npy; tests/test_gpu_rccl.py checks it)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, frame, max_bytes=DUMP_BYTES_MAX) -> None:
+    """--dump-outputs: the delivered frame (H, W, 4) as out_dir/frame.npy in
+    float32 (uint8 values convert exactly).  A frame that would pass max_bytes
+    is stored as a sample of its rows -- the same rows every run (seed 0),
+    ascending, their indices in out_dir/frame_rows.npy (float64) -- so the
+    files together stay below max_bytes."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    H = frame.shape[0]
+    row_bytes = frame[0].size * 4
+    keep = (max_bytes - 4096) // (row_bytes + 8)  # 8 B per stored row index, 4 KB for the two .npy headers
+    if H > keep:
+        rows = np.sort(np.random.default_rng(0).choice(H, size=keep, replace=False))
+        np.save(d / "frame_rows.npy", rows.astype(np.float64))
+        frame = frame[rows]
+    else:
+        (d / "frame_rows.npy").unlink(missing_ok=True)
+    np.save(d / "frame.npy", np.ascontiguousarray(frame, dtype=np.float32))
 
 
 def free_port() -> int:
@@ -335,7 +372,7 @@ def roofline(ops, alg_bytes, k_avg_s, k_launches, frames_per_launch, measured, t
     r05 item 1).  The reference-walk VALU model and the 136 B/ray HBM model
     are labelled sub-objects with a "model_ratio" (a model's count over the
     peak, which can pass 1 -- not a measured fraction)."""
-    ref_tops = ops / k_avg_s / 1e12
+    ref_tops = ops / k_avg_s / 1e12 if ops is not None else None  # None: not counted (a run without --full)
     lane_tops = measured.get("valu_lane_ops_tops") if isinstance(measured, dict) else None
     stale_tops = measured.get("stale_valu_lane_ops_tops") if isinstance(measured, dict) else None
     hw = lane_tops is not None
@@ -361,7 +398,7 @@ def roofline(ops, alg_bytes, k_avg_s, k_launches, frames_per_launch, measured, t
                    ("; 2 contexts: consecutive launches overlap, so a launch's "
                     "span includes time shared with its neighbours" if contexts > 1 else "")),
         "kernel_resources": kern_res,
-        "reference_equivalent": {
+        "reference_equivalent": None if ref_tops is None else {
             "lane_ops_tops": round(ref_tops, 3), "model_ratio": round(ref_tops / VALU_PEAK_TOPS, 4),
             "ops": ("VALU lane-ops the reference BVH walk would execute on the timed frames (SURVEY 8d "
                     "model: 25 per AABB test + 71 per rect test, counted by the BVH loop form) per launch / "
@@ -640,6 +677,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     drain()
+    if args.dump_outputs and rank == 0:  # the last timed step's frame, before the counting re-runs below
+        dump_outputs(args.dump_outputs, frame_buf.cpu().numpy())
     for r in rens:  # errors the timed launches raised on the GPU (naming the call), outside the timing
         r.sync()
     exposed_ms = float(trace_end[0].elapsed_time(assembled)) if distributed else None
@@ -658,37 +697,45 @@ def main():
         k_ms += ms
         k_launches += n
 
-    # count the rays of exactly the timed frames (deterministic re-run, untimed), and the reference BVH
-    # walk's work on the same frames (node visits = 2 AABB tests each, rect tests) with the BVH loop form,
+    # count the rays of exactly the timed frames (deterministic re-run, untimed), and with --full the reference
+    # BVH walk's work on the same frames (node visits = 2 AABB tests each, rect tests) with the BVH loop form,
     # whose counts equal the oracle's (tests/test_gpu_parity.py) -- the SURVEY 8(d) VALU model's inputs
-    rays = paths = 0
-    for i in range(args.steps):
-        st = step(i, i, stats=True)
-        rays += st.rays; paths += st.paths
-        progress(f"counting rays: frame {i + 1}/{args.steps}")
+    rays = paths = i = 0
+    if batch[0] > 1:  # in the timed launches' sizes: a launch's counts are the sums over its frames
+        for n in launch_sizes(args.steps, batch[0]):
+            st = step_batch(i, i, n, stats=True)
+            rays += st.rays; paths += st.paths
+            i += n
+            progress(f"counting rays: frame {i}/{args.steps}")
+    else:
+        for i in range(args.steps):
+            st = step(i, i, stats=True)
+            rays += st.rays; paths += st.paths
+            progress(f"counting rays: frame {i + 1}/{args.steps}")
     drain()
     from mirror_maze import MM_INFO_LEAN, MM_TRAV_LEAF_INTERIOR, MM_TRAV_LEAN
     from mirror_maze import MMError
 
-    counter = Renderer(local)
-    counter.upload_scene(scene)
-    counter.set_option(7, MM_TRAV_LEAN if counter.scene_info(MM_INFO_LEAN) else MM_TRAV_LEAF_INTERIOR)
     visits = rtests = ref_rays = 0
-    cnt_out = torch.empty((my_rows, W, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.stream(counter.own_stream()):
-        for i in range(args.steps):
-            try:
-                _, st = counter.trace_tile(u, make_ext(spp, bl, ml, frame=i), 0, y0, W, my_rows,
-                                           y_stride=y_stride, out=cnt_out, stats=True)
-            except MMError:  # form 7 needs the tree + records in LDS (N=64: form 5, the same counts)
-                counter.set_option(7, MM_TRAV_LEAF_INTERIOR)
-                _, st = counter.trace_tile(u, make_ext(spp, bl, ml, frame=i), 0, y0, W, my_rows,
-                                           y_stride=y_stride, out=cnt_out, stats=True)
-            visits += st.node_visits; rtests += st.rect_tests; ref_rays += st.rays
-            progress(f"counting reference work: frame {i + 1}/{args.steps}")
-    torch.cuda.synchronize(dev)
-    counter.close()
-    assert ref_rays == rays or args.accumulate, (ref_rays, rays)
+    if args.full:
+        counter = Renderer(local)
+        counter.upload_scene(scene)
+        counter.set_option(7, MM_TRAV_LEAN if counter.scene_info(MM_INFO_LEAN) else MM_TRAV_LEAF_INTERIOR)
+        cnt_out = torch.empty((my_rows, W, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.stream(counter.own_stream()):
+            for i in range(args.steps):
+                try:
+                    _, st = counter.trace_tile(u, make_ext(spp, bl, ml, frame=i), 0, y0, W, my_rows,
+                                               y_stride=y_stride, out=cnt_out, stats=True)
+                except MMError:  # form 7 needs the tree + records in LDS (N=64: form 5, the same counts)
+                    counter.set_option(7, MM_TRAV_LEAF_INTERIOR)
+                    _, st = counter.trace_tile(u, make_ext(spp, bl, ml, frame=i), 0, y0, W, my_rows,
+                                               y_stride=y_stride, out=cnt_out, stats=True)
+                visits += st.node_visits; rtests += st.rect_tests; ref_rays += st.rays
+                progress(f"counting reference work: frame {i + 1}/{args.steps}")
+        torch.cuda.synchronize(dev)
+        counter.close()
+        assert ref_rays == rays or args.accumulate, (ref_rays, rays)
     counts = torch.tensor([rays, paths, visits, rtests], dtype=torch.float64)
     t_el = torch.tensor([elapsed], dtype=torch.float64)
     dist_info = None
@@ -738,7 +785,8 @@ def main():
         # roofline of the dominant kernel (ray trace), rank 0's launches
         k_avg_s = (k_ms / 1e3) / max(k_launches, 1)
         per_launch = 1.0 / max(k_launches, 1)
-        ops = (OPS_PER_AABB * 2 * visits + OPS_PER_RECT * rtests) * per_launch   # reference-walk VALU model
+        # reference-walk VALU model (counted with --full)
+        ops = (OPS_PER_AABB * 2 * visits + OPS_PER_RECT * rtests) * per_launch if args.full else None
         alg_bytes = (BYTES_PER_RAY * rays + BYTES_PER_PIXEL * my_rows * W * args.steps) * per_launch
         frames_per_launch = args.steps * per_launch
         measured, traffic = pmc_profile(args, frames_per_launch, k_avg_s, world, shared=args.shared_gpu)
@@ -749,6 +797,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "samples_per_s": round(paths_all / elapsed, 1),
             "higher_is_better": True,
@@ -771,14 +820,14 @@ def main():
                                                          if calib else None),
                        "rays_per_frame": int(rays_all / args.steps), "paths_per_frame": int(paths_all / args.steps),
                        "rays_total": int(rays_all),
-                       "node_visits_per_ray": round(visits_all / max(rays_all, 1), 2),
-                       "rect_tests_per_ray": round(rtests_all / max(rays_all, 1), 2)},
+                       "node_visits_per_ray": round(visits_all / max(rays_all, 1), 2) if args.full else None,
+                       "rect_tests_per_ray": round(rtests_all / max(rays_all, 1), 2) if args.full else None},
             "roofline": roofline(ops, alg_bytes, k_avg_s, k_launches, frames_per_launch, measured, traffic,
                                  active[0], kern_res),
             "distributed": dist_info,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(scene, u, make_ext(spp, bl, ml, frame=0), W, H, args.cpu_seconds)
         json_out.write(json.dumps(line) + "\n")
         json_out.flush()

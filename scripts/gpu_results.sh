@@ -3,7 +3,7 @@
 # an 8-way split of C3 / C4 on one GPU -> gpurun_out/<tag>/<name>.json (scripts/results_table.py).
 set -o pipefail
 OUT=gpurun_out/$1; mkdir -p $OUT
-run() { local name=$1; shift; timeout -k 10 400 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -3 $OUT/$name.err; exit 1; }; echo "$name ok"; }
+run() { local name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -3 $OUT/$name.err; exit 1; }; echo "$name ok"; }
 run c1 --config c1
 run c2 --config c2
 run c3 --config c3 --steps 20 --warmup 5

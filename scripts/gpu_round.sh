@@ -30,9 +30,9 @@ case "$STEP" in
     T=${1:-final}
     bash scripts/gpu_steps.sh $T \
       "120|smoke|python -c 'import __graft_entry__ as g; g.smoke()'" \
-      "200|bench|python bench.py --steps 20 --warmup 5" || exit $?
+      "200|bench|python bench.py --full --steps 20 --warmup 5" || exit $?
     bash scripts/gpu_results.sh ${T}res || exit $?
-    timeout -k 10 300 python bench.py --config c5 --accumulate --steps 120 --warmup 1 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --config c5 --accumulate --steps 120 --warmup 1 --no-cpu-baseline \
       > gpurun_out/${T}res/c5_acc120.json 2> gpurun_out/${T}res/c5_acc120.err || exit $?
     export TMPDIR=/tmp; mkdir -p gpurun_out/${T}prof
     for C in "c2|--config c2 --steps 10 --warmup 2" "c4|--config c4 --steps 4 --warmup 1" \

@@ -26,7 +26,7 @@ print("|---|---|---|---|---|---|---|---|---|")
 
 def ratio(sub):
     """a model's count over the peak: model_ratio (round 6 on), frac in older lines"""
-    v = sub.get("model_ratio", sub.get("frac"))
+    v = sub.get("model_ratio", sub.get("frac")) if sub else None  # (null: a bench.py line without --full)
     return "—" if v is None else f"{v:.3f}"
 
 

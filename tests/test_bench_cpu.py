@@ -114,6 +114,50 @@ def test_roofline_without_a_record_is_null_not_a_model():
     assert r["reference_equivalent"]["model_ratio"] == round(40 / bench.VALU_PEAK_TOPS, 4)
 
 
+def test_roofline_of_a_plain_run_has_no_reference_walk_model():
+    """Without --full the reference walk's work is not counted: the sub-object
+    is null, the timed launches' own figures stay."""
+    import bench
+
+    r = bench.roofline(None, 1e9, 0.05, 1, 20, {"valu_lane_ops_tops": 29.0, "source": "x"}, 5, 1, {})
+    assert r["reference_equivalent"] is None
+    assert r["frac"] == round(29.0 / bench.VALU_PEAK_TOPS, 4) and r["kernel_avg_ms"] == 50.0
+    assert r["model_hbm"]["gbs"] == 20.0
+
+
+def test_dump_outputs_whole_frame_and_seeded_row_sample(tmp_path):
+    """--dump-outputs: frame.npy is the delivered frame in float32 (RGBA8 bytes
+    convert exactly); a frame above the byte limit is stored as the same
+    ascending sample of rows every time, with the row indices beside it, and
+    the files together stay below the limit."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(5)
+    frame8 = rng.integers(0, 256, size=(37, 19, 4), dtype=np.uint8)
+    bench.dump_outputs(tmp_path / "a", frame8)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["frame.npy"]
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame8.astype(np.float32))
+
+    frame = rng.random((37, 19, 4), dtype=np.float32)
+    limit = 20 * 19 * 16  # room for fewer than 20 of the 37 rows
+    for name in ("b", "c"):
+        bench.dump_outputs(tmp_path / name, frame, max_bytes=limit)
+    rows = np.load(tmp_path / "b" / "frame_rows.npy")
+    part = np.load(tmp_path / "b" / "frame.npy")
+    assert rows.dtype == np.float64 and part.dtype == np.float32
+    idx = rows.astype(np.int64)
+    assert 0 < len(idx) < 20 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 37
+    assert np.array_equal(part, frame[idx])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "frame_rows.npy"))
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= limit
+    bench.dump_outputs(tmp_path / "b", frame)  # a whole frame into the same folder: no stale row list
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["frame.npy"]
+    assert bench.DUMP_BYTES_MAX <= 64 * 10**6
+
+
 def _largs(gpus=1, launcher="auto"):
     from types import SimpleNamespace
 

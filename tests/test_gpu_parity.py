@@ -415,7 +415,8 @@ def test_plain_cell_words_option_bit_exact(gpu):
 
 def test_bench_prints_one_json_line(gpu):
     """bench.py's driver contract: exactly one JSON line on stdout with the
-    metric, the roofline and the issue mode (short C2 run)."""
+    metric, the roofline and the issue mode (short C2 run; --full: the
+    reference walk's work is counted in runs of its own)."""
     import json
     import subprocess
     import sys
@@ -423,7 +424,7 @@ def test_bench_prints_one_json_line(gpu):
 
     repo = Path(__file__).resolve().parent.parent
     r = subprocess.run([sys.executable, str(repo / "bench.py"), "--config", "c2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, cwd=repo)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -440,6 +441,44 @@ def test_bench_prints_one_json_line(gpu):
     assert d["config"]["frame_contexts"] in (1, 2)
     assert d["config"]["frames_per_launch"] == 2  # default batching: the 2 timed frames in one launch
     assert d["roofline"]["launches"] == 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_frame(gpu, tmp_path):
+    """A plain run (no --full) prints the headline fields and leaves out what
+    takes runs of its own; --dump-outputs writes the frame the last timed step
+    delivered: float32, equal to the texture-write conversion of trace_tile's
+    frame steps - 1 (C1, 3 steps in one launch)."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from mirror_maze import Renderer, default_uniform, make_ext
+
+    repo = Path(__file__).resolve().parent.parent
+    steps = 3
+    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--config", "c1", "--steps", str(steps),
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=240, cwd=repo)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "Mrays/s" and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["roofline"]["launches"] == 1 and d["config"]["frames_per_launch"] == steps
+    assert d["cpu_baseline"] is None and d["roofline"]["reference_equivalent"] is None
+    assert d["config"]["node_visits_per_ray"] is None
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["frame.npy"]
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 256, 4)
+    with Renderer(0) as ren:
+        ren.upload_scene(_scene(16))
+        want, st = ren.trace_tile(default_uniform(256, 256, 0), make_ext(1, 1, 15, frame=steps - 1), 0, 0, 256, 256,
+                                  stats=True)
+        want8 = ren.quantize(want).cpu().numpy()
+    assert np.array_equal(got, want8.astype(np.float32))
+    assert d["config"]["paths_per_frame"] == st.paths == 256 * 256
 
 
 def test_bench_issue_mode_calibration(gpu):
