@@ -141,6 +141,27 @@ int  mm_trace_tile_frames(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
                           uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                           uint32_t y_stride, float* out_dev, mm_stats* stats);
 
+/* A moving-camera frame sequence in ONE launch: mm_trace_tile_frames with a
+ * camera per frame.  Frame f (0 <= f < n_frames) is traced with camera cams[f]
+ * and RNG frame ext->frame + f into out_dev + f*w*h*4 (4-byte pixels with
+ * MM_EXT_RGBA8), and is bit-identical to mm_trace_tile called with uni->cam =
+ * cams[f] and frame = ext->frame + f; stats are summed over the frames.  The
+ * view size and chunk_w come from uni; uni->cam is ignored.  cams: HOST array
+ * of n_frames cameras (e.g. mm_player_uniform's .cam after each
+ * mm_player_step), consumed when the call returns; the context owns the device
+ * copy, which is ordered on the context's stream ahead of the launch and never
+ * shares records with an earlier call's launch that may still run.  Every
+ * condition of mm_trace_tile_frames applies (also for n_frames = 1): the
+ * wave-persistent kernel with fused resolve or tail deferral, no
+ * MM_EXT_ACCUMULATE, the 2^32 queue and 2^29 staging bounds, one row batch;
+ * MM_PIPE_REFERENCE returns MM_ERR_UNSUPPORTED, n_frames = 0 or cams = NULL
+ * MM_ERR_INVALID.  (The reference moves its camera every frame,
+ * src/main.rs:738-842, and pays one dispatch per frame.) */
+int  mm_trace_tile_cameras(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams,
+                           const mm_ext* ext, uint32_t n_frames,
+                           uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                           uint32_t y_stride, float* out_dev, mm_stats* stats);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

@@ -58,6 +58,12 @@ struct mm_ctx {
     // mirror-tail rings' records (MM_OPT_DEFER)
     void* d_tail = nullptr;
     uint32_t tail_cap = 0;
+    // camera records of mm_trace_tile_cameras launches (mm::kCamStride floats each): a pinned host staging
+    // ring and its device mirror, `cams_cap` records each, filled from `cams_next` on (mm_runtime.hip
+    // stage_cameras)
+    float* h_cams = nullptr;
+    float* d_cams = nullptr;
+    size_t cams_cap = 0, cams_next = 0;
     // aux: stats[4] (u64) + error flag (u32)
     unsigned long long* d_aux = nullptr;
     uint32_t* d_work = nullptr;  // the wave-persistent kernel's self-cleaning queue heads + waves-done word (4 KB)

@@ -87,7 +87,14 @@ struct TileJob {
     // deferred path is lost (bit 4, and the reader's ring timeout) -- tests of
     // the error path.
     uint32_t fault = 0;
+    // Camera sequence (mm_trace_tile_cameras): frame f of the launch is traced with camera record f of this
+    // device array (kCamStride floats per record: an mm_camera, padded to 64 B) instead of u.cam.  Null:
+    // u.cam for every frame.  (Last member: the offsets of the fields above are those of the launches
+    // without it.)
+    const float* cams = nullptr;
 };
+constexpr uint32_t kCamStride = 16;
+static_assert(sizeof(mm_camera) <= kCamStride * sizeof(float), "a camera record holds an mm_camera");
 
 // Error flag bits (aux word 4, and the status word's low bits).
 constexpr uint32_t kErrStack = 1u, kErrRing = 2u, kErrInjected = 8u, kErrLost = 16u, kErrPublish = 32u;

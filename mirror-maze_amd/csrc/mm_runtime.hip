@@ -142,6 +142,37 @@ int tail_queue(mm_ctx* c, TailQueue& q) {
     return MM_OK;
 }
 
+// The device records of a camera-sequence launch (mm_launch.h TileJob::cams): the caller's cameras go into a
+// pinned staging ring (consumed when this returns) and from there to the ring's device mirror by a copy on
+// the context's stream, ahead of the launch that reads them.  Every call takes fresh records, so a later
+// call's cameras never land on those of a launch still running, and nothing here waits for the GPU -- except
+// when the ring is full: then everything the device has queued is waited for once, and the ring grows (up to
+// kCamsWrap records, from where on it wraps instead).
+constexpr size_t kCamsMin = 8, kCamsWrap = 4096;
+int stage_cameras(mm_ctx* c, const mm_camera* cams, uint32_t n, const float*& dev) {
+    if (c->cams_next + n > c->cams_cap) {
+        HIPC(c, hipDeviceSynchronize());  // staged records may still be on their way, on any stream used so far
+        if (n > c->cams_cap || c->cams_cap < kCamsWrap) {
+            const size_t cap = std::max<size_t>({kCamsMin, 2 * c->cams_cap, n});
+            if (c->h_cams) (void)hipHostFree(c->h_cams);
+            (void)hipFree(c->d_cams);
+            c->h_cams = nullptr; c->d_cams = nullptr; c->cams_cap = 0;
+            HIPC(c, hipHostMalloc((void**)&c->h_cams, cap * kCamStride * sizeof(float), hipHostMallocDefault));
+            HIPC(c, hipMalloc((void**)&c->d_cams, cap * kCamStride * sizeof(float)));
+            c->cams_cap = cap;
+        }
+        c->cams_next = 0;
+    }
+    float* h = c->h_cams + c->cams_next * kCamStride;
+    std::memset(h, 0, (size_t)n * kCamStride * sizeof(float));
+    for (uint32_t f = 0; f < n; ++f) std::memcpy(h + (size_t)f * kCamStride, &cams[f], sizeof(mm_camera));
+    float* d = c->d_cams + c->cams_next * kCamStride;
+    HIPC(c, hipMemcpyAsync(d, h, (size_t)n * kCamStride * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    c->cams_next += n;
+    dev = d;
+    return MM_OK;
+}
+
 int begin_timing(mm_ctx* c) {
     HIPC(c, hipEventRecord(c->ev0, c->stream));
     return MM_OK;
@@ -344,6 +375,8 @@ void mm_destroy(mm_ctx* c) {
     (void)hipFree(c->d_fb8_alt); (void)hipFree(c->d_packets);
     (void)hipFree(c->d_samples); (void)hipFree(c->d_aux); (void)hipFree(c->d_tail); (void)hipFree(c->d_work);
     (void)hipFree(c->d_gather);
+    (void)hipFree(c->d_cams);
+    if (c->h_cams) (void)hipHostFree(c->h_cams);
     if (c->gather_done) (void)hipEventDestroy(c->gather_done);
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -766,9 +799,14 @@ int choose_wavepersist(mm_ctx* c, DevScene& sc, int& form, int& mode) {
     return MM_OK;
 }
 
-int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_frames, uint32_t x0, uint32_t y0,
-                    uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev, mm_stats* stats) {
+// cams: null, or the n_frames cameras of a camera-sequence launch (mm_trace_tile_cameras; u->cam is then unused)
+int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
+                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev,
+                    mm_stats* stats) {
     if (!c) return MM_ERR_INVALID;
+    // the multi-frame entry point this call came through (its conditions apply to a one-camera sequence too)
+    const bool multi = n_frames > 1 || cams;
+    const std::string fn = cams ? "mm_trace_tile_cameras" : "mm_trace_tile_frames";
     // an earlier call that failed on the GPU is reported first, by name; this call is then not enqueued
     if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
     if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_tile: no scene uploaded");
@@ -783,7 +821,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
         return fail(c, MM_ERR_INVALID, "mm_trace_tile: bounce or mirror limit above 32767");
     if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H)
         return fail(c, MM_ERR_INVALID, "mm_trace_tile: tile outside the frame");
-    if (n_frames == 0) return fail(c, MM_ERR_INVALID, "mm_trace_tile_frames: no frames");
+    if (n_frames == 0) return fail(c, MM_ERR_INVALID, fn + ": no frames");
     // MM_EXT_RGBA8: 4-byte RGBA8 pixels (the fused texture-write conversion) instead of float4
     const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
     if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
@@ -849,7 +887,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
     const bool fusable = persist && c->opt_fuse && 64 % e->spp == 0;
     // staging bound: a multi-frame launch stages all its frames at once; past kStagePathsMax it runs without
     // the rings (fused resolve) if it can
-    if (defer && n_frames > 1 && tile_paths * n_frames > kStagePathsMax && fusable && !wave) defer = false;
+    if (defer && multi && tile_paths * n_frames > kStagePathsMax && fusable && !wave) defer = false;
     // wave-persistent kernel with whole pixels per 64-path chunk: resolve fused
     const bool fuse = fusable && !defer;
     // Rows per launch: the fused resolve needs no staging (one launch covers up to 2^31 paths, a whole C5
@@ -858,28 +896,29 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
     const uint64_t batch_paths = fuse ? (1ull << 31) : defer ? kStagePathsMax : (64ull << 20);
     const uint32_t rows_per_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(h, batch_paths / row_paths));
     if (row_paths * rows_per_batch > 0xFFFFFFFFull) return fail(c, MM_ERR_INVALID, "mm_trace_tile: row too large");
-    if (n_frames > 1) {
+    if (multi) {
         // several frames in one launch: the wave-persistent kernel's queue, with the fused resolve or
         // (tail deferral) samples staged per frame
         if (!fuse && !defer)
-            return fail(c, MM_ERR_UNSUPPORTED, "mm_trace_tile_frames: needs the wave-persistent kernel with the "
-                                               "fused resolve (64 % spp == 0) or tail deferral");
+            return fail(c, MM_ERR_UNSUPPORTED, fn + ": needs the wave-persistent kernel with the "
+                                                    "fused resolve (64 % spp == 0) or tail deferral");
         if (e->flags & MM_EXT_ACCUMULATE)
-            return fail(c, MM_ERR_INVALID, "mm_trace_tile_frames: frames of one launch cannot accumulate into "
-                                           "one image");
+            return fail(c, MM_ERR_INVALID, fn + ": frames of one launch cannot accumulate into one image");
         const uint64_t queue = ((tile_paths + 63) / 64) * 64 * n_frames;
         if (queue + (1ull << 24) > 0xFFFFFFFFull)
-            return fail(c, MM_ERR_INVALID, "mm_trace_tile_frames: more paths than one launch holds (2^32)");
+            return fail(c, MM_ERR_INVALID, fn + ": more paths than one launch holds (2^32)");
         if (defer && tile_paths * n_frames > kStagePathsMax)
-            return fail(c, MM_ERR_INVALID, "mm_trace_tile_frames: the frames' staged samples exceed 6 GiB "
-                                           "(2^29 paths) per launch; use fewer frames per launch");
-        if (rows_per_batch < h) return fail(c, MM_ERR_INVALID, "mm_trace_tile_frames: tile too large for one launch");
+            return fail(c, MM_ERR_INVALID, fn + ": the frames' staged samples exceed 6 GiB (2^29 paths) per "
+                                                "launch; use fewer frames per launch");
+        if (rows_per_batch < h) return fail(c, MM_ERR_INVALID, fn + ": tile too large for one launch");
     }
     int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap,
                                    (size_t)(row_paths * rows_per_batch) * (defer ? n_frames : 1));
     if (rc) return rc;
     TailQueue tq;
     if (defer && ring == 1 && (rc = tail_queue(c, tq))) return rc;  // (records in LDS: no global ring)
+    const float* cams_dev = nullptr;
+    if (cams && (rc = stage_cameras(c, cams, n_frames, cams_dev))) return rc;
     // aux: [0..3] stats (zeroed only when counted), [4] error flag (moved into the launch's status word by
     // the launch itself).  d_work: the wave-persistent kernel's queue head(s) and waves-done word
     // (self-cleaning).  No fill kernel on the default path: see k_trace_wavepersist.
@@ -903,6 +942,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
         job.wave_ts_cap = c->wave_ts_cap;
         job.out = reinterpret_cast<char*>(out_dev) + (size_t)j0 * w * out_bpp;
         job.n_frames = n_frames;
+        job.cams = cams_dev;
         job.reserve_cus = c->opt_reserve_cus;
         job.fault = (c->opt_fault == 1 || c->opt_fault == 4) ? (uint32_t)c->opt_fault : 0u;
         if (c->opt_fault == 2) job.ring_spin = 0;
@@ -975,9 +1015,9 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
     c->last_defer = defer;
     if (c->launch_seq > first_launch) {  // the launches this call enqueued (all of them unless rc)
         char what[160];
-        snprintf(what, sizeof(what), "%s, frames %u..%u, tile (%u, %u) %ux%u / %u, %u spp", n_frames > 1 ?
-                 "mm_trace_tile_frames" : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0, y0, w, h,
-                 y_stride, e->spp);
+        snprintf(what, sizeof(what), "%s, frames %u..%u, tile (%u, %u) %ux%u / %u, %u spp",
+                 multi ? fn.c_str() : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0, y0, w, h, y_stride,
+                 e->spp);
         c->pending.push_back({call_id, first_launch, c->launch_seq - first_launch, what, 0u});
     }
     if (rc) return rc;
@@ -993,12 +1033,20 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_
 
 int mm_trace_tile(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t x0, uint32_t y0, uint32_t w,
                   uint32_t h, uint32_t y_stride, float* out_dev, mm_stats* stats) {
-    return trace_tile_impl(c, u, e, 1, x0, y0, w, h, y_stride, out_dev, stats);
+    return trace_tile_impl(c, u, nullptr, e, 1, x0, y0, w, h, y_stride, out_dev, stats);
 }
 
 int mm_trace_tile_frames(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_frames, uint32_t x0,
                          uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev, mm_stats* stats) {
-    return trace_tile_impl(c, u, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
+    return trace_tile_impl(c, u, nullptr, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
+}
+
+int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
+                          uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev,
+                          mm_stats* stats) {
+    if (!c) return MM_ERR_INVALID;
+    if (!cams) return fail(c, MM_ERR_INVALID, "mm_trace_tile_cameras: no cameras");
+    return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
 }
 
 int mm_sync(mm_ctx* c) {

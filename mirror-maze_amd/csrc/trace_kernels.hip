@@ -456,7 +456,25 @@ __device__ __forceinline__ uint32_t dequeue(uint32_t* work, uint32_t n_queue) {
     return next;
 }
 
-template <bool kStats, typename Q>
+// The uniform a new-path chunk of frame fr is traced with.  Camera-sequence launches (kCams,
+// mm_trace_tile_cameras) take the camera from record fr of job.cams, per chunk: a claim of kClaimChunks
+// chunks straddles a frame boundary whenever cpf % kClaimChunks != 0.  fr comes from a readfirstlane'd queue
+// index and job.cams from the kernel arguments, so the address is wave-uniform; read through the constant
+// address space the ten floats are scalar loads and sit in SGPRs as the kernel-argument camera does, and
+// primary_dir's arithmetic is unchanged.  (The records are written by a copy that precedes the launch on
+// its stream and by nothing while it runs.)  Tail chunks need no camera: a parked path carries ori and dir.
+__device__ __forceinline__ mm_uniform chunk_uniform(const TileJob& job, uint32_t fr) {
+    mm_uniform u = job.u;
+    typedef const float __attribute__((address_space(4))) cam_float;
+    cam_float* r = (cam_float*)(job.cams + (size_t)fr * kCamStride);
+    u.cam.center[0] = r[0]; u.cam.center[1] = r[1]; u.cam.center[2] = r[2];
+    u.cam.focal = r[3];
+    u.cam.quat[0] = r[4]; u.cam.quat[1] = r[5]; u.cam.quat[2] = r[6]; u.cam.quat[3] = r[7];
+    u.cam.viewport[0] = r[8]; u.cam.viewport[1] = r[9];
+    return u;
+}
+
+template <bool kStats, bool kCams, typename Q>
 __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q& q, const TileJob& job,
                                                      Sample* __restrict__ samples, unsigned long long* stats,
                                                      uint32_t* err, uint32_t* work) {
@@ -489,8 +507,14 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
             PathState p;
             p.seed = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
-            p.dir = jitter(primary_dir(job.u, px, py), p.seed);
-            p.ori = ori;
+            if constexpr (kCams) {  // ori is not loop-invariant in a camera sequence
+                const mm_uniform cu = chunk_uniform(job, fr);
+                p.dir = jitter(primary_dir(cu, px, py), p.seed);
+                p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
+            } else {
+                p.dir = jitter(primary_dir(job.u, px, py), p.seed);
+                p.ori = ori;
+            }
             p.T = F3{1.0f, 1.0f, 1.0f};
             p.L = F3{0.0f, 0.0f, 0.0f};
             p.n = 0;
@@ -537,7 +561,7 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
 // last up to bounce_limit + mirror_limit iterations, would need a bound that a
 // valid 32767-bounce chunk outlasts).  A tail chunk runs the same bounce loop
 // as a new one (and may defer again) -- one copy of the loop in the kernel.
-template <bool kStats, bool kLdsPay, typename Q>
+template <bool kStats, bool kLdsPay, bool kCams, typename Q>
 __device__ __forceinline__ uint32_t wavepersist_ring_body(const DevScene& sc, const Q& q, const TileJob& job,
                                               Sample* __restrict__ samples, unsigned long long* stats, uint32_t* err,
                                               uint32_t* work) {
@@ -613,8 +637,14 @@ __device__ __forceinline__ uint32_t wavepersist_ring_body(const DevScene& sc, co
                 const uint32_t j = pix / job.w, i = pix - j * job.w;
                 const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
                 p.seed = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
-                p.dir = jitter(primary_dir(job.u, px, py), p.seed);
-                p.ori = ori;
+                if constexpr (kCams) {
+                    const mm_uniform cu = chunk_uniform(job, fr);
+                    p.dir = jitter(primary_dir(cu, px, py), p.seed);
+                    p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
+                } else {
+                    p.dir = jitter(primary_dir(job.u, px, py), p.seed);
+                    p.ori = ori;
+                }
                 p.T = F3{1.0f, 1.0f, 1.0f};
                 p.L = F3{0.0f, 0.0f, 0.0f};
                 p.n = 0;
@@ -882,7 +912,9 @@ hipError_t launch_publish_status(uint32_t* err, uint32_t* status, hipStream_t s)
 #endif
 constexpr uint32_t kWpThreads = MM_WP_THREADS;
 // kRing: 0 no tail deferral; 1 tail rings, payload in global records; 2 tail rings, payload in LDS.
-template <bool kStats, int kLds, int kForm, int kRing>
+// kCams: a camera-sequence launch (job.cams); the static-camera instances' code is the same with and without
+// the feature (gate: profiles/camera_sequence/kernel_resources.txt).
+template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false>
 __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersist(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                                unsigned long long* stats, uint32_t* err,
                                                                uint32_t* work) {
@@ -902,9 +934,9 @@ __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersis
 #endif
     const uint32_t chunks = stage_and_run<kLds, kForm, kStats, kRing>(sc, job, [&](const auto& q) {
         if constexpr (kRing != 0)
-            return wavepersist_ring_body<kStats, kRing == 2>(sc, q, job, samples, stats, err, work);
+            return wavepersist_ring_body<kStats, kRing == 2, kCams>(sc, q, job, samples, stats, err, work);
         else
-            return wavepersist_body<kStats>(sc, q, job, samples, stats, err, work);
+            return wavepersist_body<kStats, kCams>(sc, q, job, samples, stats, err, work);
     });
 #ifdef MM_LANE_STATS
     __syncthreads();  // every wave of the block is done: add its counts to the timeline buffer
@@ -954,6 +986,9 @@ static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, S
     const size_t lds = (kLds == 11 || kLds == 14) ? 0 : wavepersist_lds_bytes(sc, kLds);
     auto kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing>
                             : k_trace_wavepersist<false, kLds, kForm, kRing>;
+    if (job.cams)
+        kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing, true>
+                           : k_trace_wavepersist<false, kLds, kForm, kRing, true>;
     const uint32_t grid =
         persistent_grid(kern, lds, job.reserve_cus, (uint64_t)job.w * job.h * job.e.spp * job.n_frames);
     if (!grid) return hipErrorInvalidValue;

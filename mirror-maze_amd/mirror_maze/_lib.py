@@ -114,6 +114,8 @@ EXPORTS = {
                                 C.c_uint32, C.c_uint32, C.c_uint32, P, C.POINTER(mm_stats)]),
     "mm_trace_tile_frames": (C.c_int, [P, C.POINTER(mm_uniform), C.POINTER(mm_ext), C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.POINTER(mm_stats)]),
+    "mm_trace_tile_cameras": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.POINTER(mm_stats)]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

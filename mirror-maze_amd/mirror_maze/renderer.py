@@ -202,6 +202,45 @@ class Renderer:
                                                y_stride, out.data_ptr(), C.byref(st)))
         return out, (st if stats else None)
 
+    @staticmethod
+    def _cameras(cameras) -> np.ndarray:
+        """(n, 10) float32 camera records (sizeof(mm_camera) = 40 B per row) from
+        an (n, 10) array or a sequence of mm_camera / mm_uniform (its .cam)."""
+        if isinstance(cameras, np.ndarray):
+            cams = np.ascontiguousarray(cameras, dtype=np.float32)
+        else:
+            rows = [np.frombuffer(bytes(getattr(c, "cam", c)), dtype=np.float32) for c in cameras]
+            cams = np.stack(rows) if rows else np.zeros((0, 10), dtype=np.float32)
+        if cams.ndim != 2 or cams.shape[1] != 10:
+            raise ValueError("cameras must be mm_camera / mm_uniform values or an (n, 10) float32 array")
+        return cams
+
+    def trace_tile_cameras(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, x0: int, y0: int,
+                           w: int, h: int, y_stride: int = 1, out=None, stats: bool = False, rgba8: bool = False):
+        """Render a moving-camera sequence of a tile in ONE launch
+        (mm_trace_tile_cameras): frame f with cameras[f] and RNG frame ext.frame
+        + f, into a (n_frames, h, w, 4) float32 CUDA tensor (allocated if None;
+        uint8 RGBA8 with rgba8 / a uint8 `out`, as trace_tile).  `cameras`: a
+        sequence of mm_camera or mm_uniform (its .cam), or an (n, 10) float32
+        array such as scene.walk_cameras returns; view size and chunk_w come
+        from `uniform`, its .cam is ignored.  Frame f equals trace_tile with
+        uniform.cam = cameras[f] and frame ext.frame + f.  Returns (out,
+        mm_stats summed over the frames or None)."""
+        import torch
+
+        cams = self._cameras(cameras)
+        n = cams.shape[0]
+        out, r8 = self._out(out, (n, h, w, 4), rgba8, f"cuda:{self.device}")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
+        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
+        st = _lib.mm_stats()
+        self._check(lib().mm_trace_tile_cameras(self._ctx, C.byref(uniform), cams.ctypes.data if n else None,
+                                                C.byref(e), n, x0, y0, w, h, y_stride, out.data_ptr(),
+                                                C.byref(st)))
+        return out, (st if stats else None)
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the

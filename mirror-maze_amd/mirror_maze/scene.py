@@ -158,6 +158,20 @@ class Player:
         return u
 
 
+def walk_cameras(player: Player, script) -> np.ndarray:
+    """Walk `player` along `script`, a sequence of (keys, mouse_dx) per frame:
+    one Player.step per frame, and the camera AFTER each step -- what the
+    reference's event loop would have rendered (input handling precedes the
+    dispatch, src/main.rs:738-885).  Returns the (n, 10) float32 camera array
+    (row = mm_camera: center, focal, quat, viewport) that
+    Renderer.trace_tile_cameras takes."""
+    cams = np.zeros((len(script), 10), dtype=np.float32)
+    for f, (keys, mouse_dx) in enumerate(script):
+        player.step(keys, mouse_dx)
+        cams[f] = np.frombuffer(bytes(player.uniform().cam), dtype=np.float32)
+    return cams
+
+
 def check_collision(nodes: np.ndarray, bmin, bmax) -> int:
     """check_collision (src/main.rs:265-291): first leaf overlapping the box, or -1."""
     nodes = np.ascontiguousarray(nodes)

@@ -5,6 +5,11 @@ traces --frames frames in one multi-frame launch (bench.py's issue mode) when
 the fused resolve applies, else one launch per frame.
 
     python scripts/ab_bench.py [--config c3] [--frames 5] [--reps 2] [variant ...]
+    python scripts/ab_bench.py --camera-path [--config c3] [--frames 20] [--reps 3] [variant ...]
+--camera-path times a moving-camera sequence (a Player walking into the maze,
+one camera per frame) two ways -- ONE trace_tile_cameras launch, and one
+trace_tile call per frame (what a fly-through cost before that call existed)
+-- and, for context, the static-camera trace_tile_frames launch.
 A different build of the library: MIRROR_MAZE_LIB=/path/lib.so (scripts/ab.py).
 """
 from __future__ import annotations
@@ -49,6 +54,62 @@ VARIANTS = {
 }
 
 
+def camera_path(a, scene, cfg):
+    """Wall-clock ms/frame (enqueue to sync, after a warm-up run of the same
+    kind) of the same camera sequence as one launch and as per-frame calls."""
+    import torch
+
+    from mirror_maze import Player, Renderer, default_uniform, make_ext, mm_uniform, walk_cameras
+
+    maze_n, W, H, spp, bl, ml, desc = cfg
+    # forward into the maze, a mouse turn every 5th frame (scripts/flythrough.py's walk, at 6 key events a frame)
+    script = [([Player.KEY_W] * 6, [30.0] if f % 5 == 4 else []) for f in range(a.frames)]
+    cams = walk_cameras(Player(scene, W, H), script)
+    u = default_uniform(W, H, 0)
+    us = []
+    for c in cams:
+        v = mm_uniform.from_buffer_copy(u)
+        v.cam = type(v.cam).from_buffer_copy(c.tobytes())
+        us.append(v)
+    exts = [make_ext(spp, bl, ml, frame=1 + f) for f in range(a.frames)]
+
+    def run(r, mode, out):
+        if mode == "cameras":
+            r.trace_tile_cameras(u, cams, exts[0], 0, 0, W, H, out=out)
+        elif mode == "static":
+            r.trace_tile_frames(u, exts[0], a.frames, 0, 0, W, H, out=out)
+        else:
+            for f in range(a.frames):
+                r.trace_tile(us[f], exts[f], 0, 0, W, H, out=out[f])
+
+    print(f"# camera path: {a.frames} frames, centre {cams[0, :3]} -> {cams[-1, :3]}", flush=True)
+    for name in a.variants:
+        pipe, opts = VARIANTS[name]
+        r = Renderer(0)
+        r.set_pipeline(pipe)
+        for k, v in opts.items():
+            r.set_option(k, v)
+        r.upload_scene(scene)
+        outs = {m: torch.zeros((a.frames, H, W, 4), dtype=torch.float32, device="cuda")
+                for m in ("cameras", "per-frame")}
+        outs["static"] = outs["per-frame"]  # (timed before per-frame overwrites it)
+        for rep in range(a.reps + 1):  # rep 0 warms up
+            for mode in ("cameras", "static", "per-frame"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(r, mode, outs[mode])
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) / a.frames * 1e3
+                if rep:
+                    print(f"{name:16s} rep {rep - 1} {mode:10s} {ms:8.3f} ms/frame", flush=True)
+        same = torch.equal(outs["cameras"].view(torch.int32), outs["per-frame"].view(torch.int32))
+        print(f"{name:16s} one launch vs per-frame calls: {'bit-identical' if same else 'MISMATCH'}", flush=True)
+        r.close()
+        if not same:
+            return 1
+    return 0
+
+
 def main():
     import torch
 
@@ -60,10 +121,17 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--ranks", type=int, default=1, help="trace rank 0's rows of an N-way split (0, N, 2N, ...)")
-    ap.add_argument("variants", nargs="*", default=["default", "bvh-lean"])
+    ap.add_argument("--camera-path", action="store_true",
+                    help="time a moving-camera sequence as one trace_tile_cameras launch and as per-frame calls")
+    ap.add_argument("variants", nargs="*", default=None)
     a = ap.parse_args()
     maze_n, W, H, spp, bl, ml, desc = CONFIGS[a.config]
     scene = Scene.build(maze_n, 0)
+    if a.camera_path:
+        a.variants = a.variants or ["default"]
+        print(f"# {desc}: {scene.n_rects} rects", flush=True)
+        return camera_path(a, scene, CONFIGS[a.config])
+    a.variants = a.variants or ["default", "bvh-lean"]
     u = default_uniform(W, H, 0)
     h = (H + a.ranks - 1) // a.ranks
     base = None
@@ -111,4 +179,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

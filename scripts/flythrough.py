@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""A scripted fly-through of the maze, rendered as a moving-camera sequence.
+
+Builds an N x N maze, walks a Player along a key script (forward, with a mouse
+turn every --turn-every frames; the reference's event loop, src/main.rs:738-842)
+and renders the frames --batch per launch as RGBA8 through
+Renderer.trace_tile_cameras (mm_trace_tile_cameras: one camera per frame, one
+launch per batch), written as PNGs.
+
+    python scripts/flythrough.py --maze 32 --frames 40 --batch 20 --out flythrough/
+    python scripts/flythrough.py --maze 10 --frames 30 --no-render     # the camera path only: no GPU
+
+The camera path is printed one frame per line (floats as %.9g, which a float32
+survives): frame, center, quat -- the camera after that frame's step.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "mirror-maze_amd"))
+sys.path.insert(0, str(REPO))
+
+
+def key_script(n_frames: int, turn_every: int, turn_dx: float):
+    """(keys, mouse_dx) per frame: W held down, a mouse move of turn_dx on every
+    turn_every-th frame (walls stop the player; the turns get it moving again)."""
+    from mirror_maze import Player
+
+    return [([Player.KEY_W], [turn_dx] if turn_every and f % turn_every == turn_every - 1 else [])
+            for f in range(n_frames)]
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--maze", type=int, default=32, help="maze size N (N x N cells)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--frames", type=int, default=40)
+    ap.add_argument("--batch", type=int, default=20, help="frames per trace_tile_cameras launch")
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=8)
+    ap.add_argument("--bounces", type=int, default=8)
+    ap.add_argument("--mirrors", type=int, default=8)
+    ap.add_argument("--turn-every", type=int, default=8, help="a mouse turn every that many frames (0: never)")
+    ap.add_argument("--turn-dx", type=float, default=40.0, help="the turn's mouse deltaX")
+    ap.add_argument("--out", default="flythrough", help="folder for frame_NNNN.png")
+    ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
+    a = ap.parse_args(argv)
+    if a.frames < 1 or a.batch < 1:
+        ap.error("--frames and --batch must be positive")
+
+    from mirror_maze import Player, Scene, walk_cameras
+
+    scene = Scene.build(a.maze, a.seed)
+    player = Player(scene, a.width, a.height)
+    script = key_script(a.frames, a.turn_every, a.turn_dx)
+    cams = walk_cameras(player, script)
+    for f, c in enumerate(cams):
+        print(f"frame {f} center {c[0]:.9g} {c[1]:.9g} {c[2]:.9g} quat {c[4]:.9g} {c[5]:.9g} {c[6]:.9g} {c[7]:.9g}")
+    if a.no_render:
+        return 0
+
+    import torch
+
+    from mirror_maze import Renderer, make_ext
+    from mirror_maze.io import write_png
+
+    out_dir = Path(a.out)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    u = player.uniform()  # view size and chunk width; its camera is not used
+    with Renderer(0) as r:
+        r.upload_scene(scene)
+        for f0 in range(0, a.frames, a.batch):
+            batch = cams[f0:f0 + a.batch]
+            e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
+            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=True)
+            r.sync()
+            frames = img.cpu().numpy()
+            for k in range(len(batch)):
+                write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
+            print(f"# frames {f0}..{f0 + len(batch) - 1}: one launch, {out_dir}/frame_{f0:04d}.png ...", flush=True)
+    torch.cuda.synchronize()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
