@@ -162,6 +162,53 @@ int  mm_trace_tile_cameras(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* 
                            uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                            uint32_t y_stride, float* out_dev, mm_stats* stats);
 
+/* ---- closest-hit answers for the caller ------------------------------------
+ * The trace calls above return shaded, averaged colour only.  These two
+ * return what the rays hit.  Both are enqueued on the context's stream like
+ * the trace calls, take a call number (mm_last_call / mm_call_status / mm_sync
+ * report their GPU-side errors), and run the query method MM_PIPE_AUTO and
+ * MM_OPT_TRAVERSAL select for the scene -- the certified grid search with the
+ * BVH walk as its fallback, or BVH loop form 7 / 5; MM_PIPE_REFERENCE: the
+ * straight reference walk -- over the scene in global memory (MM_OPT_LDS_*
+ * select nothing here).  Every method returns the reference walk's answer,
+ * bit for bit.
+ *
+ * mm_query_rays: a batch of caller-supplied rays (line of sight, picking,
+ * collision).  rays_dev: DEVICE pointer, 16-byte aligned, 8 floats per ray:
+ * (ox, oy, oz, -, dx, dy, dz, -), the two w components ignored.  hits_dev:
+ * DEVICE pointer, 8-byte aligned, per ray (float t, uint32_t k): the pair
+ * intersect_bvh_iterative (src/shaders.metal:115-156) ends with when started
+ * at t = 1e30 -- the closest rect k with t > 0.1 --, or (1e30f, MM_AOV_ID_MISS).
+ * Any ray is allowed (origins outside the scene or on a wall, zero direction
+ * components, unnormalised directions).  A ray whose traversal stack overflows
+ * gets (1e30f, MM_AOV_ID_FAILED), never a wrong hit, and the call reports
+ * MM_ERR_STACK.  n_rays = 0: MM_OK, nothing enqueued. */
+int  mm_query_rays(mm_ctx* ctx, const float* rays_dev, uint64_t n_rays, void* hits_dev);
+
+/* Per-pixel feature buffers (AOVs) of the tile (x0 + i, y0 + j*y_stride) of
+ * mm_trace_tile, for n_frames cameras in one launch: what each pixel sees.
+ * The path of the pixel-CENTRE ray (no jitter) is followed through the mirror
+ * chain -- a mirror bounce is deterministic, src/shaders.metal:326-330 -- to
+ * the first surface that shades diffusely, with the bounce loop's operations:
+ *   ori = cam.center, dir = the primary direction, mh = 0, dist = 0; loop:
+ *   query; nothing hit -> MISS.  Hit rect k at t: n = normalize(cross(v, u)),
+ *   sg = sign(dot(dir, n)), dist += t; matte, or a mirror seen from behind
+ *   (sg == 1) -> SURFACE; else if mh + 1 < mirror_limit: ori += t dir, dir =
+ *   normalize(reflect(dir, n)), ++mh, again; else -> MIRROR_END.
+ * mirror_limit: 0..32767 as mm_ext.mirror_limit; <= 1 gives plain first-hit
+ * buffers.  Outputs (mm_aov: any may be NULL, not all), element f*w*h + j*w + i:
+ *   normal_depth  (-sg * n, dist)            MISS: (0, 0, 0, 1e30f)
+ *   albedo        (rect colour, (float)mh)   MISS: (0, 0, 0, (float)mh)
+ *   id            k | MM_AOV_ID_SURFACE or k | MM_AOV_ID_MIRROR_END; MM_AOV_ID_MISS
+ * bit-identical to the same loop over the reference walk.  cams: NULL (the one
+ * camera uni->cam; n_frames must be 1) or a HOST array of n_frames cameras,
+ * consumed on return (the staging of mm_trace_tile_cameras: back-to-back calls
+ * neither wait nor share records); view size from uni.  A failed query gives
+ * id MM_AOV_ID_FAILED and MM_ERR_STACK, as in mm_query_rays. */
+int  mm_trace_aov(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams, uint32_t n_frames,
+                  uint32_t mirror_limit, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                  uint32_t y_stride, const mm_aov* out);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

@@ -82,6 +82,22 @@ typedef struct mm_stats {
     uint64_t paths;         /* samples traced                                 */
 } mm_stats;
 
+/* Feature buffers of mm_trace_aov (mm_api.h): three optional DEVICE pointers,
+ * each NULL or n_frames * w * h elements, frame-major, row-major over the
+ * tile.  normal_depth and albedo hold float4 (16-byte aligned), id uint32.   */
+typedef struct mm_aov {
+    float*    normal_depth; /* (side * n, distance along the mirror chain)    */
+    float*    albedo;       /* (rect colour, mirror hits before the surface)  */
+    uint32_t* id;           /* rect index | kind << 30, MM_AOV_ID_*           */
+} mm_aov;
+
+/* mm_aov.id and mm_query_rays' k */
+#define MM_AOV_ID_MISS       0xFFFFFFFFu  /* nothing hit                        */
+#define MM_AOV_ID_FAILED     0xFFFFFFFEu  /* no answer: the call reports MM_ERR_STACK */
+#define MM_AOV_ID_SURFACE    0x40000000u  /* | k: a surface that shades diffusely */
+#define MM_AOV_ID_MIRROR_END 0x80000000u  /* | k: a mirror's front, mirror_limit reached */
+#define MM_AOV_ID_RECT       0x00FFFFFFu  /* mask of k                          */
+
 /* Return codes (0 = success; never panics or throws across the ABI). */
 #define MM_OK               0
 #define MM_ERR_INVALID     -1  /* bad argument / shape                        */

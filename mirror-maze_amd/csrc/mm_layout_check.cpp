@@ -23,5 +23,7 @@ static_assert(offsetof(mm_uniform, view_w) == 40 && offsetof(mm_uniform, view_h)
               "Uniform field offsets");
 static_assert(sizeof(mm_ext) == 24, "mm_ext is 24 B");
 static_assert(sizeof(mm_stats) == 32, "mm_stats is 32 B");
+static_assert(sizeof(mm_aov) == 24 && offsetof(mm_aov, albedo) == 8 && offsetof(mm_aov, id) == 16,
+              "mm_aov is three pointers");
 
 extern "C" int mm_layout_ok(void) { return 1; }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "grid_build.h"
+#include "mm_aov.h"
 #include "mm_api.h"
 #include "mm_ctx.h"
 #include "mm_launch.h"
@@ -1047,6 +1048,140 @@ int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams,
     if (!c) return MM_ERR_INVALID;
     if (!cams) return fail(c, MM_ERR_INVALID, "mm_trace_tile_cameras: no cameras");
     return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
+}
+
+namespace {
+
+// Query policy of mm_query_rays / mm_trace_aov (aov_kernels.hip): the method choose_wavepersist would take
+// for the scene and MM_OPT_TRAVERSAL, without its LDS placements -- those kernels read the scene from global
+// memory, where every grid form and both BVH forms exist.
+int aov_policy(mm_ctx* c, int& policy) {
+    if (c->pipe == MM_PIPE_REFERENCE) {
+        policy = kAovRef;
+        return MM_OK;
+    }
+    const bool auto_form = c->opt_ww < 0;
+    const int form = auto_form ? (c->grid_ok ? kFormGrid : (c->lean_ok ? kFormLean : kFormLeafInterior)) : c->opt_ww;
+    if (form == kFormGrid) {
+        if (!c->grid_ok)
+            return fail(c, MM_ERR_UNSUPPORTED, "grid search unavailable for this scene: " + c->grid_why);
+        const bool slow = !c->lean_ok || c->grid_slow;  // general rect tests for the SLOW records
+        if (c->grid_flat && slow) return fail(c, MM_ERR_UNSUPPORTED, "maze grid with SLOW records");
+        policy = kAovGrid + (slow ? kAovGridSlow : 0) + (c->grid_wide ? kAovGridWide : 0) +
+                 (c->grid_flat ? kAovGridFlat : 0);
+    } else if (form == kFormLean) {
+        if (!c->lean_ok && !auto_form)
+            return fail(c, MM_ERR_UNSUPPORTED, "loop form 7 needs compact records for every rect");
+        policy = c->lean_ok ? kAovBvhLean : kAovBvhLi;
+    } else {
+        policy = kAovBvhLi;
+    }
+    if (!aov_policy_built(policy))
+        return fail(c, MM_ERR_UNSUPPORTED, "query policy " + std::to_string(policy) + " not built");
+    return MM_OK;
+}
+
+// One numbered call of one kernel launch + the publish of its error flag into the call's status word
+// (trace_tile_impl's protocol for a non-persistent kernel).  launch(err_dev) enqueues the kernel.
+extern "C++" template <typename L>
+int enqueue_query_call(mm_ctx* c, const std::string& what, const char* name, L&& launch) {
+    int rc = begin_timing(c);
+    if (rc) return rc;
+    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
+    const uint64_t call_id = ++c->call_seq, first_launch = c->launch_seq;
+    uint32_t* status = nullptr;
+    if ((rc = next_status(c, status))) return rc;
+    if ((rc = prof_mark(c))) {
+        c->h_status[first_launch % kStatusSlots] = kStatusDone;  // nothing will write this slot
+        return rc;
+    }
+    const hipError_t le = launch(err_dev);
+    if (le != hipSuccess) {
+        c->h_status[first_launch % kStatusSlots] = kStatusDone;
+        return fail(c, MM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(le));
+    }
+    c->pending.push_back({call_id, first_launch, 1, what, 0u});
+    const hipError_t pe = launch_publish_status(err_dev, status, c->stream);
+    if (pe != hipSuccess) {
+        // fold the kernel's error flag into this launch's slot after a sync (trace_tile_impl)
+        uint32_t bits = 0;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipMemcpy(&bits, err_dev, sizeof(bits), hipMemcpyDeviceToHost);
+        (void)hipMemset(err_dev, 0, sizeof(bits));
+        __atomic_store_n(c->h_status + first_launch % kStatusSlots, bits | kErrPublish | kStatusDone,
+                         __ATOMIC_RELEASE);
+        return fail(c, MM_ERR_HIP, std::string("launch_publish_status: ") + hipGetErrorString(pe));
+    }
+    if ((rc = prof_mark(c))) return rc;
+    return end_timing(c, 2);
+}
+
+}  // namespace
+
+int mm_query_rays(mm_ctx* c, const float* rays_dev, uint64_t n_rays, void* hits_dev) {
+    if (!c) return MM_ERR_INVALID;
+    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
+    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_query_rays: no scene uploaded");
+    if (n_rays == 0) return MM_OK;
+    if (!rays_dev || !hits_dev) return fail(c, MM_ERR_INVALID, "mm_query_rays: null argument");
+    if (reinterpret_cast<uintptr_t>(rays_dev) % 16 || reinterpret_cast<uintptr_t>(hits_dev) % 8)
+        return fail(c, MM_ERR_INVALID, "mm_query_rays: rays not 16-byte or hits not 8-byte aligned");
+    if (n_rays > aov_max_items()) return fail(c, MM_ERR_INVALID, "mm_query_rays: more rays than one launch holds");
+    HIPC(c, hipSetDevice(c->device));
+    int policy = 0;
+    if (int rc = aov_policy(c, policy)) return rc;
+    const DevScene sc = dev_scene(c);
+    char what[96];
+    snprintf(what, sizeof(what), "mm_query_rays, %llu rays", (unsigned long long)n_rays);
+    return enqueue_query_call(c, what, "launch_query_rays", [&](uint32_t* err_dev) {
+        return launch_query_rays(sc, policy, reinterpret_cast<const float4*>(rays_dev), n_rays,
+                                 reinterpret_cast<RayHit*>(hits_dev), err_dev, c->stream);
+    });
+}
+
+int mm_trace_aov(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, uint32_t n_frames, uint32_t mirror_limit,
+                 uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, const mm_aov* out) {
+    if (!c) return MM_ERR_INVALID;
+    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
+    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_aov: no scene uploaded");
+    if (!u || !out) return fail(c, MM_ERR_INVALID, "mm_trace_aov: null argument");
+    if (!out->normal_depth && !out->albedo && !out->id) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no output");
+    if (n_frames == 0) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no frames");
+    if (!cams && n_frames > 1) return fail(c, MM_ERR_INVALID, "mm_trace_aov: several frames need their cameras");
+    if (!(u->view_w >= 1.0f && u->view_w <= 65536.0f && u->view_h >= 1.0f && u->view_h <= 65536.0f))
+        return fail(c, MM_ERR_INVALID, "mm_trace_aov: bad view size");
+    const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
+    if (w == 0 || h == 0 || y_stride == 0) return fail(c, MM_ERR_INVALID, "mm_trace_aov: empty tile");
+    if (mirror_limit > 32767) return fail(c, MM_ERR_INVALID, "mm_trace_aov: mirror limit above 32767");
+    if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H)
+        return fail(c, MM_ERR_INVALID, "mm_trace_aov: tile outside the frame");
+    if (reinterpret_cast<uintptr_t>(out->normal_depth) % 16 || reinterpret_cast<uintptr_t>(out->albedo) % 16 ||
+        reinterpret_cast<uintptr_t>(out->id) % 4)
+        return fail(c, MM_ERR_INVALID, "mm_trace_aov: float4 outputs not 16-byte or id not 4-byte aligned");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (n_pix > 0x7FFFFFFFull || (n_pix + 255) / 256 * n_frames > 0x7FFFFFFFull)
+        return fail(c, MM_ERR_INVALID, "mm_trace_aov: more pixels than one launch holds");
+    HIPC(c, hipSetDevice(c->device));
+    int policy = 0;
+    if (int rc = aov_policy(c, policy)) return rc;
+    AovJob job;
+    job.u = *u;
+    job.cams = nullptr;
+    if (cams)
+        if (int rc = stage_cameras(c, cams, n_frames, job.cams)) return rc;
+    job.n_frames = n_frames;
+    job.mirror_limit = mirror_limit;
+    job.x0 = x0; job.y0 = y0; job.w = w; job.h = h; job.y_stride = y_stride;
+    job.normal_depth = reinterpret_cast<float4*>(out->normal_depth);
+    job.albedo = reinterpret_cast<float4*>(out->albedo);
+    job.id = out->id;
+    const DevScene sc = dev_scene(c);
+    char what[160];
+    snprintf(what, sizeof(what), "mm_trace_aov, %u frames, tile (%u, %u) %ux%u / %u, mirror limit %u", n_frames, x0,
+             y0, w, h, y_stride, mirror_limit);
+    return enqueue_query_call(c, what, "launch_trace_aov", [&](uint32_t* err_dev) {
+        return launch_trace_aov(sc, policy, job, err_dev, c->stream);
+    });
 }
 
 int mm_sync(mm_ctx* c) {

@@ -48,6 +48,8 @@ MM_PLAYER_COLLIDED, MM_PLAYER_ROTATED, MM_PLAYER_NAN_QUAT = 1, 2, 4
 MM_BVH_SWEEP, MM_BVH_EXHAUSTIVE = 0, 1
 MM_OWN_STREAM = C.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF).value  # (void*)-1
 MM_COMM_ID_BYTES, MM_GATHER_SELF_VIA_RCCL = 128, 1
+MM_AOV_ID_MISS, MM_AOV_ID_FAILED, MM_AOV_ID_RECT = 0xFFFFFFFF, 0xFFFFFFFE, 0x00FFFFFF
+MM_AOV_ID_SURFACE, MM_AOV_ID_MIRROR_END = 0x40000000, 0x80000000
 
 
 class mm_rect(C.Structure):
@@ -76,6 +78,10 @@ class mm_ext(C.Structure):
 class mm_stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("node_visits", C.c_uint64), ("rect_tests", C.c_uint64),
                 ("paths", C.c_uint64)]
+
+
+class mm_aov(C.Structure):
+    _fields_ = [("normal_depth", C.c_void_p), ("albedo", C.c_void_p), ("id", C.c_void_p)]
 
 
 class mm_rng(C.Structure):
@@ -116,6 +122,9 @@ EXPORTS = {
                                        C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.POINTER(mm_stats)]),
     "mm_trace_tile_cameras": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.POINTER(mm_stats)]),
+    "mm_query_rays": (C.c_int, [P, P, C.c_uint64, P]),
+    "mm_trace_aov": (C.c_int, [P, C.POINTER(mm_uniform), P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                               C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mm_aov)]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

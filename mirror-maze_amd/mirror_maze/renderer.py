@@ -241,6 +241,70 @@ class Renderer:
                                                 C.byref(st)))
         return out, (st if stats else None)
 
+    # -- closest-hit answers -------------------------------------------------
+    def query_rays(self, rays, out=None):
+        """Closest hit of each of n caller-supplied rays (mm_query_rays).
+        `rays`: (n, 2, 4) float32 CUDA tensor or array, ray i = (origin xyz, -),
+        (direction xyz, -).  Returns (t, k): float32 and int32 views of an
+        (n, 2) int32 CUDA tensor (`out` if given) -- the reference walk's
+        answer, k's bits those of the uint32 rect index, MM_AOV_ID_MISS
+        (t = 1e30) where nothing is hit."""
+        import torch
+
+        dev = torch.device(f"cuda:{self.device}")
+        if not torch.is_tensor(rays):
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float32)).to(dev)
+        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous() and rays.dim() == 3
+                and tuple(rays.shape[1:]) == (2, 4)):
+            raise ValueError("rays must be a contiguous float32 (n, 2, 4) CUDA tensor or array")
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.int32, device=rays.device)
+        elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (n, 2)):
+            raise ValueError("out must be a contiguous int32 (n, 2) CUDA tensor")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(rays.device).cuda_stream))
+        self._check(lib().mm_query_rays(self._ctx, rays.data_ptr() if n else None, n, out.data_ptr() if n else None))
+        return out[:, 0].view(torch.float32), out[:, 1]
+
+    AOV_NAMES = ("normal_depth", "albedo", "id")
+
+    def trace_aov(self, uniform: _lib.mm_uniform, cameras=None, mirror_limit: int = 15, *, x0: int, y0: int,
+                  w: int, h: int, y_stride: int = 1, want=AOV_NAMES, out=None):
+        """Per-pixel feature buffers of a tile (mm_trace_aov): the pixel-centre
+        ray followed through the mirror chain to the first surface that shades
+        diffusely.  `cameras`: None (uniform.cam, one frame) or what
+        trace_tile_cameras takes (one frame per camera, one launch).  Returns a
+        dict of the buffers named in `want`, CUDA tensors (taken from the dict
+        `out` where it has them):
+          normal_depth  (n_frames, h, w, 4) float32: outward normal, distance
+          albedo        (n_frames, h, w, 4) float32: rect colour, mirror hits
+          id            (n_frames, h, w)    int32:   rect | MM_AOV_ID_* bits"""
+        import torch
+
+        want = tuple(want)
+        if not want or any(k not in self.AOV_NAMES for k in want):
+            raise ValueError(f"want must name some of {self.AOV_NAMES}")
+        cams = None if cameras is None else self._cameras(cameras)
+        n = 1 if cams is None else cams.shape[0]
+        dev = torch.device(f"cuda:{self.device}")
+        bufs = {}
+        for k in want:
+            shape, dt = ((n, h, w), torch.int32) if k == "id" else ((n, h, w, 4), torch.float32)
+            t = (out or {}).get(k)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=dev)
+            elif not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"out[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
+            bufs[k] = t
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(dev).cuda_stream))
+        a = _lib.mm_aov(*[bufs[k].data_ptr() if k in bufs else None for k in self.AOV_NAMES])
+        self._check(lib().mm_trace_aov(self._ctx, C.byref(uniform), None if cams is None else
+                                       (cams.ctypes.data if n else None), n, mirror_limit, x0, y0, w, h, y_stride,
+                                       C.byref(a)))
+        return bufs
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the

@@ -9,6 +9,13 @@ launch per batch), written as PNGs.
 
     python scripts/flythrough.py --maze 32 --frames 40 --batch 20 --out flythrough/
     python scripts/flythrough.py --maze 10 --frames 30 --no-render     # the camera path only: no GPU
+    python scripts/flythrough.py --maze 32 --frames 40 --aov aov/       # + feature buffers per frame
+
+--aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
+what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
+distance along the mirror chain, 1e30 where nothing is hit) and id.npy (uint32
+rect index | kind << 30) through Renderer.trace_aov (mm_trace_aov, --mirrors as
+its mirror limit): the inputs a denoiser or a compositor takes beside the frame.
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -47,6 +54,8 @@ def main(argv=None) -> int:
     ap.add_argument("--turn-every", type=int, default=8, help="a mouse turn every that many frames (0: never)")
     ap.add_argument("--turn-dx", type=float, default=40.0, help="the turn's mouse deltaX")
     ap.add_argument("--out", default="flythrough", help="folder for frame_NNNN.png")
+    ap.add_argument("--aov", metavar="DIR", default=None,
+                    help="also write per-frame feature buffers: DIR/frame_NNNN/{normal.png,depth.npy,id.npy}")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
@@ -63,10 +72,11 @@ def main(argv=None) -> int:
     if a.no_render:
         return 0
 
+    import numpy as np
     import torch
 
     from mirror_maze import Renderer, make_ext
-    from mirror_maze.io import write_png
+    from mirror_maze.io import quantize, write_png
 
     out_dir = Path(a.out)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -82,6 +92,21 @@ def main(argv=None) -> int:
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
             print(f"# frames {f0}..{f0 + len(batch) - 1}: one launch, {out_dir}/frame_{f0:04d}.png ...", flush=True)
+            if a.aov is None:
+                continue
+            bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height, want=("normal_depth", "id"))
+            r.sync()
+            nd = bufs["normal_depth"].cpu().numpy()
+            ids = bufs["id"].cpu().numpy().view(np.uint32)
+            for k in range(len(batch)):
+                d = Path(a.aov) / f"frame_{f0 + k:04d}"
+                d.mkdir(parents=True, exist_ok=True)
+                rgba = np.concatenate([0.5 * nd[k, ..., :3] + 0.5, np.ones_like(nd[k, ..., :1])], axis=-1)
+                write_png(d / "normal.png", quantize(rgba))
+                np.save(d / "depth.npy", nd[k, ..., 3])
+                np.save(d / "id.npy", ids[k])
+            print(f"# frames {f0}..{f0 + len(batch) - 1}: feature buffers, one launch, {a.aov}/frame_{f0:04d}/ ...",
+                  flush=True)
     torch.cuda.synchronize()
     return 0
 
