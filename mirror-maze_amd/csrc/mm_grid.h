@@ -32,7 +32,14 @@
 // The exact per-rect operations (the compact records of rect_compact.cpp)
 // give each rect's a, so the minimum and whether it is attained twice are
 // exact.  scripts/grid_sim.c replays every query of a C3 frame (137 M) on
-// the CPU against the reference walk: 0 differences.
+// the CPU against the reference walk: 0 differences.  Where delta + eta is
+// largest against the cells -- rects in the faces of the grid box itself,
+// bounce rays that leave them at |d . n| < 2^-6, rays starting on the box's
+// faces, edges and corners, a scene 2^6 extents from the origin (eps a
+// sixteenth of a cell), cell boundaries on and off the rects' lattice --
+// tests/test_gpu_grid_stress.py (case B) compares the 3-D walk with the
+// reference walk, and tests/test_gpu_aov.py's query test runs arbitrary rays
+// through the SLOW records and the lattice soup's ties.
 //
 // Face ranges (64-bit cell words): a cell entered through face f tests only
 // the entries the neighbour across f -- the cell visited just before -- does
@@ -477,7 +484,12 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
         // the grid in the same instant): such a cell meets the ray in one point,
         // which lies on the face of the cell just tested, so the lists' eps
         // covers it (header) and the answer is unchanged.  (CPU replay of every
-        // query of a C3 frame: scripts/grid_sim.c TEND=1.)
+        // query of a C3 frame: scripts/grid_sim.c TEND=1.  tests/test_gpu_grid_stress.py,
+        // case C, aims rays at it on N=10 and N=64: |d.x| == |d.z| with equal
+        // offsets, so that tx == tz step after step; rays that end at te == tend;
+        // and rays that cross an interior x boundary at the very time of the last
+        // z boundary -- the skipped cell.  tests/test_grid_stress.py counts each
+        // on a float32 restatement of the two fmas.)
         const float sgx = r.y.x > 0.0f ? 1.0f : -1.0f, sgz = r.y.z > 0.0f ? 1.0f : -1.0f;
         float fbx = (float)bx, fbz = (float)bz;  // (exact small integers)
         const float tend = fminf(ty, fminf(__builtin_fmaf(r.y.x > 0.0f ? g.nf[0] : 0.0f, Bx, Ax),

@@ -31,11 +31,26 @@ struct BvhQuery {
 // global memory (lean loop form, compact records) when the search cannot
 // certify its answer (a tie, a failed leaf-box check) or the ray is outside
 // the Markstein guards or the grid.  hit_origin: the ray starts at a hit
-// point (a bounce ray), which lies inside the grid box -- the point is on a
-// rect up to the rounding of the reference's bounds test and of ori + t dir
-// (a few u C), and the grid box is the box of every rect corner widened by
-// eps = 2^-14 C (grid_build.cpp) -- so the box check runs only in a wave
-// holding a ray from the camera.
+// point (a bounce ray), and the box check runs only in a wave holding a ray
+// from the camera.  A hit point is on a rect up to the rounding of the
+// reference's bounds test and of ori + t dir, i.e. up to a few ulp of
+// max(|ori|, t): a few u C -- far inside the grid box, which is the box of
+// every rect corner widened by eps = 2^-14 C (grid_build.cpp) -- when the
+// previous ray started in or near the scene, but ulp(D) when a camera at
+// distance D sent it, which passes eps from D = 2^10 C on.  The search does
+// not need the origin inside the box: grid_first clamps the start cell per
+// axis, so the walk follows the ray's point clamped into the box, whose cells
+// include every cell the ray itself crosses (no rect reaches outside the
+// box), the crossing times are those of the true origin, and a ray heading
+// away from the box steps out of the grid (or reaches tend) at its first
+// step.  What is then not enforced is org_ok's |o| <= 2^60, which
+// ray_fast_ok_boxed leaves to the box check: a hit point is within a few
+// ulp(D) of a rect of a scene inside 2^60 (grid_build.cpp), so it passes 2^60
+// only from D > 2^83 on, where neighbouring float directions are 2^59 apart
+// at the scene (no test reaches that).
+// tests/test_gpu_grid_stress.py (case A) compares such rays with the walk:
+// bounce origins up to four cells outside the box, in every tile a quarter
+// to all of them (tests/test_grid_stress.py states the shares).
 template <bool kStats, bool kSlow, bool kWide, bool kFlat, typename GV>
 struct GridQuery {
     const DevScene& sc;

@@ -16,16 +16,28 @@ CORRIDOR = HERE / "golden" / "aov_corridor.npz"
 MISS, FAILED, SURFACE, MIRROR_END, RECT = 0xFFFFFFFF, 0xFFFFFFFE, 1 << 30, 2 << 30, 0x00FFFFFF
 
 
-def build_ref(tmp_dir) -> C.CDLL:
+def build_ref(tmp_dir, twin: bool = False) -> C.CDLL:
     """Compile tests/aov_ref.c (which includes oracle/mm_oracle.c) into tmp_dir
-    with the oracle Makefile's CFLAGS and bind it."""
+    with the oracle Makefile's CFLAGS and bind it.  twin: the build over
+    oracle/grid_cpu.c -- the same entry points answered by the CPU twin of the
+    certified grid search (class Twin)."""
     mk = (REPO / "oracle" / "Makefile").read_text()
     cflags = re.search(r"^CFLAGS\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
-    so = Path(tmp_dir) / "libaov_ref.so"
-    subprocess.run(["gcc", *cflags, "-Wno-unused-function", "-shared", "-o", str(so), str(HERE / "aov_ref.c"), "-lm"],
-                   check=True)
+    so = Path(tmp_dir) / ("libaov_twin.so" if twin else "libaov_ref.so")
+    subprocess.run(["gcc", *cflags, *(["-DAOVREF_TWIN"] if twin else []), "-Wno-unused-function", "-shared", "-o",
+                    str(so), str(HERE / "aov_ref.c"), "-lm"], check=True)
     L = C.CDLL(str(so))
     P = C.c_void_p
+    L.aovref_walk_ties.argtypes = [P, C.c_int, P, C.c_uint64, P, P, P]
+    L.aovref_walk_ties.restype = None
+    L.oracle_trace_tile.argtypes = [P, P, P] + [C.c_uint32] * 5 + [P, P]
+    if twin:
+        L.gridcpu_build.argtypes = [P]
+        L.gridcpu_stats.argtypes = [P, C.c_int]
+        L.gridcpu_stats.restype = None
+    else:
+        L.aovref_record.argtypes = [P, C.c_uint64]
+        L.aovref_record.restype = C.c_uint64
     L.aovref_query.argtypes = [P, P, P, P, P]
     L.aovref_query_batch.argtypes = [P, P, C.c_uint64, P]
     L.aovref_pixel.argtypes = [P, P, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P]
@@ -71,6 +83,60 @@ class Ref:
         assert self.L.aovref_tile(C.byref(self.o.sc), ub, mirror_limit, x0, y0, w, h, y_stride, nd.ctypes.data,
                                   al.ctypes.data, ids.ctypes.data) == 0
         return {"normal_depth": nd, "albedo": al, "id": ids}
+
+    def trace_tile(self, uniform, ext, x0, y0, w, h, y_stride=1):
+        """oracle_trace_tile of this library: ((h, w, 4) float32, Stats)."""
+        from oracle.oracle import Stats
+
+        out, st = np.zeros((h, w, 4), np.float32), Stats()
+        ub, eb = C.create_string_buffer(bytes(uniform), 56), C.create_string_buffer(bytes(ext), len(bytes(ext)))
+        assert self.L.oracle_trace_tile(C.byref(self.o.sc), ub, eb, x0, y0, w, h, y_stride, out.ctypes.data,
+                                        C.byref(st)) == 0
+        return out, st
+
+    def recorded(self, fn, cap=1 << 20):
+        """(fn()'s result, the queries the reference walk answered meanwhile):
+        an (n, 8) float32 array of (o.xyz, t, d.xyz, bits of k), in order; a
+        path's first query starts at the camera, every later one at the
+        float32 ori + t * dir of the one before."""
+        rec = np.zeros((cap, 8), np.float32)
+        self.L.aovref_record(rec.ctypes.data, cap)
+        try:
+            res = fn()
+        finally:
+            n = self.L.aovref_record(None, 0)
+        assert n <= cap, (n, cap)
+        return res, rec[:n].copy()
+
+    def walk_ties(self, grid, flat, rays, best):
+        """aovref_walk_ties: dict of the walk restatement's counts (aov_ref.c)."""
+        g = np.float32(list(grid["mn"]) + list(grid["cell"]) + [float(x) for x in grid["n"]] + list(grid["mx"]))
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        best = np.ascontiguousarray(best, dtype=np.float32)
+        out = (C.c_uint64 * 5)()
+        flags = np.zeros(rays.shape[0], np.uint8)
+        self.L.aovref_walk_ties(g.ctypes.data, 1 if flat else 0, rays.ctypes.data, rays.shape[0], best.ctypes.data, out,
+                                flags.ctypes.data)
+        w = dict(zip(("tied_steps", "ended_at_tend", "entered_at_exit", "walked", "steps"), [int(x) for x in out]))
+        w["flags"] = flags  # per ray: 1 a tied step, 2 ended at tend / left the grid, 4 entered a cell at the exit
+        return w
+
+
+class Twin(Ref):
+    """The same entry points over oracle/grid_cpu.c (build_ref(twin=True)): the
+    CPU twin of the certified grid search, with its walk fallback.  The
+    library keeps one grid: making a Twin builds its scene's and zeroes the
+    counts, so a Twin is used up before the next one is made."""
+
+    def __init__(self, L, scene):
+        super().__init__(L, scene)
+        assert L.gridcpu_build(C.byref(self.o.sc)) == 0
+
+    def stats(self, reset=False):
+        """Queries since the build or the last reset: {"grid", "fallback", "other_scene"}."""
+        out = (C.c_uint64 * 3)()
+        self.L.gridcpu_stats(out, 1 if reset else 0)
+        return {"grid": out[0], "fallback": out[1], "other_scene": out[2]}
 
 
 def corridor():

@@ -47,10 +47,11 @@ def _scene(name):
         if name == "corridor":
             s, u = A.corridor()
             u.view_w, u.view_h = VIEW_CORRIDOR
-        elif name == "soup":
+        elif name in ("soup", "lattice"):
             from test_gpu_random_scene import random_scene
 
-            s, u = random_scene(3000, 7, False), default_uniform(*VIEW_WIDE, 0)
+            s = random_scene(3000, 11, True) if name == "lattice" else random_scene(3000, 7, False)
+            u = default_uniform(*VIEW_WIDE, 0)
         elif name == "maze64":
             s, u = Scene.build(64, 0), default_uniform(*VIEW_WIDE, 0)
         else:
@@ -282,8 +283,11 @@ def _rays(scene, n, seed):
 
 
 @pytest.mark.parametrize("policy", ["auto", "trav7-lds1", "trav5-lds0", "reference"])
-@pytest.mark.parametrize("name", ["maze10", "corridor"])
+@pytest.mark.parametrize("name", ["maze10", "corridor", "soup", "lattice"])
 def test_query_rays_bit_exact(gpu, ref_lib, name, policy):
+    """soup and lattice: the 3-D walk, the general (SLOW) rect test and the
+    lattice's tie fallback under caller-supplied rays (tests/test_grid_stress.py
+    has the share of each ray kind the search answers)."""
     from mirror_maze import MMError, _lib
 
     s, _ = _scene(name)
