@@ -17,6 +17,8 @@
 // instance of trace_kernels.hip is compiled differently for it.
 #include <hip/hip_runtime.h>
 
+#include <utility>
+
 #include "grid_build.h"
 #include "mm_aov.h"
 #include "mm_launch.h"
@@ -205,39 +207,46 @@ __global__ __launch_bounds__(1024) void k_trace_aov_lds(DevScene sc, AovJob job,
 }
 #endif
 
-// The instances: the reference walk, the two BVH forms, and the grid search's
-// slow / wide / flat forms (no slow maze form: choose_wavepersist's rule).
-#define MM_AOV_POLICIES(X)                                                                                   \
-    X(kAovRef) X(kAovBvhLi) X(kAovBvhLean) X(kAovGrid) X(kAovGrid + kAovGridSlow) X(kAovGrid + kAovGridWide) \
-    X(kAovGrid + kAovGridWide + kAovGridSlow) X(kAovGrid + kAovGridFlat) X(kAovGrid + kAovGridFlat + kAovGridWide)
+uint64_t aov_max_items() { return (uint64_t)0x7FFFFFFFu * kAovThreads; }
 
-bool aov_policy_built(int policy) {
-#define MM_AOV(P) if (policy == (P)) return true;
+// The built policies (mm_variants.h) as one table: per policy the two kernels' instances.
+constexpr int kAovKeys[] = {
+#define MM_AOV(P) (P),
     MM_AOV_POLICIES(MM_AOV)
 #undef MM_AOV
-    return false;
+};
+constexpr size_t kAovCount = sizeof(kAovKeys) / sizeof(kAovKeys[0]);
+struct AovTable {
+    void (*query[kAovCount])(DevScene, const float4*, uint64_t, RayHit*, uint32_t*);
+    void (*aov[kAovCount])(DevScene, AovJob, uint32_t*);
+};
+template <size_t... I>
+static AovTable aov_table(std::index_sequence<I...>) {
+    return {{k_query_rays<kAovKeys[I]>...}, {k_trace_aov<kAovKeys[I]>...}};
 }
+static const AovTable kAovTable = aov_table(std::make_index_sequence<kAovCount>{});
 
-uint64_t aov_max_items() { return (uint64_t)0x7FFFFFFFu * kAovThreads; }
+// The table's row, or kAovCount when the policy is not built.
+static size_t find_variant(int policy) {
+    size_t i = 0;
+    while (i < kAovCount && kAovKeys[i] != policy) ++i;
+    return i;
+}
 
 hipError_t launch_query_rays(const DevScene& sc, int policy, const float4* rays, uint64_t n_rays, RayHit* hits,
                              uint32_t* err, hipStream_t s) {
-    if (n_rays == 0 || n_rays > aov_max_items()) return hipErrorInvalidValue;
+    const size_t v = find_variant(policy);
+    if (v == kAovCount || n_rays == 0 || n_rays > aov_max_items()) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)((n_rays + kAovThreads - 1) / kAovThreads));
-#define MM_AOV(P)                                                                                            \
-    if (policy == (P)) {                                                                                     \
-        hipLaunchKernelGGL(k_query_rays<(P)>, grid, dim3(kAovThreads), 0, s, sc, rays, n_rays, hits, err);   \
-        return hipGetLastError();                                                                            \
-    }
-    MM_AOV_POLICIES(MM_AOV)
-#undef MM_AOV
-    return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kAovTable.query[v], grid, dim3(kAovThreads), 0, s, sc, rays, n_rays, hits, err);
+    return hipGetLastError();
 }
 
 hipError_t launch_trace_aov(const DevScene& sc, int policy, const AovJob& job, uint32_t* err, hipStream_t s) {
     const uint64_t n_pix = (uint64_t)job.w * job.h;
     const uint64_t bpf = (n_pix + kAovThreads - 1) / kAovThreads;
-    if (n_pix == 0 || n_pix > 0x7FFFFFFFu || job.n_frames == 0 || bpf * job.n_frames > 0x7FFFFFFFu)
+    const size_t v = find_variant(policy);
+    if (v == kAovCount || n_pix == 0 || n_pix > 0x7FFFFFFFu || job.n_frames == 0 || bpf * job.n_frames > 0x7FFFFFFFu)
         return hipErrorInvalidValue;
 #ifdef MM_AOV_AB_LDS
     if (policy == kAovGrid + kAovGridFlat + kAovGridWide && sc.grid.bytes <= 64 * 1024) {
@@ -251,14 +260,8 @@ hipError_t launch_trace_aov(const DevScene& sc, int policy, const AovJob& job, u
     }
 #endif
     const dim3 grid((uint32_t)(bpf * job.n_frames));
-#define MM_AOV(P)                                                                                            \
-    if (policy == (P)) {                                                                                     \
-        hipLaunchKernelGGL(k_trace_aov<(P)>, grid, dim3(kAovThreads), 0, s, sc, job, err);                   \
-        return hipGetLastError();                                                                            \
-    }
-    MM_AOV_POLICIES(MM_AOV)
-#undef MM_AOV
-    return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kAovTable.aov[v], grid, dim3(kAovThreads), 0, s, sc, job, err);
+    return hipGetLastError();
 }
 
 }  // namespace mm

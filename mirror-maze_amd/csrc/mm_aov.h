@@ -18,17 +18,7 @@ constexpr uint32_t kHitFailed = 0xFFFFFFFEu;  // the traversal stack overflowed 
 // id buffer: k | kind << 30 (k < 2^24, mm_upload_scene)
 constexpr uint32_t kAovSurface = 1u << 30, kAovMirrorEnd = 2u << 30;
 
-// Query policy of the two kernels: the method MM_OPT_TRAVERSAL / the scene
-// select (mm_runtime.hip aov_policy), always over the global-memory views
-// (grid placement 13, BVH placement 0: profiles/aov/ab.txt).
-enum AovPolicy : int {
-    kAovRef = 0,        // MM_PIPE_REFERENCE: RefQuery
-    kAovBvhLi = 1,      // BVH loop form 5
-    kAovBvhLean = 2,    // BVH loop form 7 (compact records)
-    kAovGrid = 3,       // + kAovGridSlow | kAovGridWide | kAovGridFlat: the certified grid search
-    kAovGridSlow = 1, kAovGridWide = 2, kAovGridFlat = 4,
-};
-bool aov_policy_built(int policy);
+// (Query policies of the two kernels, enum AovPolicy, and aov_policy_built: mm_variants.h.)
 
 struct AovJob {
     mm_uniform u;

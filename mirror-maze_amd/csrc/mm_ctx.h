@@ -5,11 +5,11 @@
 
 #include <hip/hip_runtime.h>
 
-#include <deque>
 #include <string>
 #include <vector>
 
 #include "mm_api.h"
+#include "mm_calls.h"
 #include "mm_launch.h"
 
 using mm::DevGrid;
@@ -88,21 +88,11 @@ struct mm_ctx {
     bool prof = false;
     std::vector<hipEvent_t> prof_ev;   // pairs (start, stop)
     size_t prof_used = 0;              // events recorded since last reset
-    // Per-launch status words (host-mapped pinned memory): launch L of the
-    // context writes slot L % kStatusSlots when it ends (error bits |
-    // kStatusDone).  Each mm_trace_tile* call is a numbered "call" owning a
-    // run of launches; a call whose launches raised an error is reported,
-    // naming the call, by the next call on the context, mm_sync or
-    // mm_call_status -- never blamed on a later call's work.
+    // Per-launch status words (host-mapped pinned memory, kStatusSlots + kRingDiagWords of them) and the
+    // numbered calls that own them: mm_calls.h.
     uint32_t* h_status = nullptr;
     uint32_t* d_status = nullptr;
-    std::vector<uint64_t> slot_owner;  // launch id + 1 holding each slot, 0 = free
-    uint64_t launch_seq = 0, call_seq = 0;
-    struct Call { uint64_t id, first, n; std::string what; uint32_t bits; };
-    struct Failed { uint64_t id; uint32_t bits; std::string what; bool reported; };
-    std::deque<Call> pending;
-    std::deque<Failed> failed;  // the last kFailedKept failed calls
-    uint64_t failed_dropped = 0;  // highest call id dropped from `failed` (older ids: status no longer kept)
+    mm::CallTracker calls;
     int opt_fault = 0;           // MM_OPT_FAULT_INJECT
     bool opt_grid_merge = true;  // MM_OPT_GRID_MERGE (read by mm_upload_scene)
     int opt_grid_cell = 100;     // MM_OPT_GRID_CELL (read by mm_upload_scene)

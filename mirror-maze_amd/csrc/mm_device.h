@@ -9,21 +9,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "grid_build.h"
 #include "mm_types.h"
+#include "mm_variants.h"
 
 namespace mm {
 
 constexpr float kBig = 1e30f;     // shaders.metal:15, 94, 149 (IR 0x46293E5940000000)
 constexpr int kStackMax = 50;     // shaders.metal:123
 
-// Diagnostics build (-DMM_LANE_STATS, scripts/lane_probe.py): per phase of the
-// bounce loop, the wave-iterations that run it and the lanes active in them,
-// counted in block-local LDS words and added to the wave-timeline buffer at
-// exit.  Not a product build: the counting perturbs the timing.
-enum LanePhase : int {
-    kLpChunk, kLpBounce, kLpGlobal, kLpGridIter, kLpRectTest, kLpCellStep, kLpCert, kLpFallback,
-    kLpShade, kLpDiffuse, kLpTrial, kLpMirror, kLpCount
-};
+// (enum LanePhase: mm_variants.h)
 constexpr uint32_t kLaneStatRecord = 49152;  // wave-timeline record (4 x u64) where the totals start
 #ifdef MM_LANE_STATS
 __device__ __forceinline__ uint32_t* lane_stat_words() {
@@ -42,18 +37,7 @@ __device__ __forceinline__ void lane_stat(int ph) {
 #define MM_LANE_STAT(ph) ((void)0)
 #endif
 
-// Closest-hit query methods of the wave-persistent kernel (MM_OPT_TRAVERSAL):
-// BVH loop forms (mm_trace.h) and the certified grid search (mm_grid.h).
-// kFormGridSlow (internal): the grid search on a scene with SLOW rect records.
-// kFormGridWide / kFormGridWideSlow (internal): the same on a grid with 64-bit
-// cell words (per-face list ranges; grid_build.cpp).
-// kFormGridFlat (internal, + kFormGrid..kFormGridWideSlow): the same on a grid
-// with one cell along y (the walk steps x / z only; mm_grid.h kFlat).
-enum : int {
-    kFormIfIf = 0, kFormLeafInterior = 5, kFormLean = 7,
-    kFormGrid = 11, kFormGridSlow = 12, kFormGridWide = 13, kFormGridWideSlow = 14,
-    kFormGridFlat = 4  // offset: 15..18
-};
+// The query forms (kForm*): mm_variants.h.
 __host__ __device__ constexpr bool grid_form(int f) { return f >= kFormGrid && f <= kFormGridWideSlow + kFormGridFlat; }
 __host__ __device__ constexpr bool grid_flat(int f) { return f > kFormGridWideSlow; }
 __host__ __device__ constexpr int grid_base(int f) { return grid_flat(f) ? f - kFormGridFlat : f; }
@@ -107,6 +91,31 @@ struct DevGrid {
     int nm1[3];
     float nf[3];               // n[a] as a float (the maze forms' end time: a kernel argument, not a hoisted convert)
 };
+// The device view of a built grid (grid_build.h) whose image was copied to `image_dev`.
+inline DevGrid dev_grid(const GridHost& gh, const uint8_t* image_dev) {
+    DevGrid dg{};
+    for (int a = 0; a < 3; ++a) {
+        dg.mn[a] = gh.mn[a]; dg.mx[a] = gh.mx[a]; dg.cell[a] = gh.cell[a]; dg.inv[a] = gh.inv[a];
+        dg.n[a] = gh.n[a];
+        dg.nm1[a] = gh.n[a] - 1;
+        dg.nf[a] = (float)gh.n[a];
+    }
+    dg.n_glob = gh.n_glob;
+    dg.slab = gh.slab ? 1u : 0u;
+    dg.slab_y[0] = gh.slab_y[0];
+    dg.slab_y[1] = gh.slab_y[1];
+    for (int i = 0; i < 4; ++i) dg.glob[i] = gh.glob[i];
+    dg.cells = image_dev;
+    dg.list = reinterpret_cast<const uint16_t*>(image_dev + gh.off_list);
+    dg.recs = reinterpret_cast<const uint4*>(image_dev + gh.off_recs);
+    dg.box = reinterpret_cast<const float2*>(image_dev + gh.off_box);
+    dg.image = reinterpret_cast<const uint4*>(image_dev);
+    dg.off_list = gh.off_list; dg.off_recs = gh.off_recs; dg.off_box = gh.off_box; dg.bytes = gh.bytes;
+    dg.off_class = gh.off_class;  // 0: 32-byte records, no class table
+    dg.off_data = gh.off_data;
+    dg.cls = gh.off_class ? reinterpret_cast<const float4*>(image_dev + gh.off_class) : nullptr;
+    return dg;
+}
 
 struct DevScene {
     const float4* nodes;      // 2 * n_nodes, production layout

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "mm_calls.h"
 #include "mm_device.h"
 
 namespace mm {
@@ -28,8 +29,7 @@ static_assert(sizeof(Sample) == 12, "three floats, no padding");
 // (n - mh) | mh << 15 | bank << 30, sample slot, s1 -- one base pointer; 16 SoA field arrays would
 // hold 15 addresses in SGPRs across the bounce loop), `cap` records; resident
 // block b owns the kTailRing records from b * kTailRing (its tail ring, at most
-// 2 blocks per CU).
-constexpr uint32_t kTailRing = 512;
+// 2 blocks per CU; kTailRing: mm_variants.h).
 
 struct TailQueue {
     uint4* rec = nullptr;
@@ -96,10 +96,7 @@ struct TileJob {
 constexpr uint32_t kCamStride = 16;
 static_assert(sizeof(mm_camera) <= kCamStride * sizeof(float), "a camera record holds an mm_camera");
 
-// Error flag bits (aux word 4, and the status word's low bits).
-constexpr uint32_t kErrStack = 1u, kErrRing = 2u, kErrInjected = 8u, kErrLost = 16u, kErrPublish = 32u;
-constexpr uint32_t kStatusDone = 0x80000000u;
-
+// (Error flag bits kErr* and kStatusDone: mm_calls.h.)
 // One-thread kernel that publishes a non-persistent launch's error flag into
 // its status word (the persistent kernel's last wave does this itself).
 hipError_t launch_publish_status(uint32_t* err, uint32_t* status, hipStream_t s);
@@ -124,12 +121,7 @@ hipError_t launch_trace_wavepersist(const DevScene& sc, const TileJob& job, Samp
                                     unsigned long long* stats, uint32_t* err, uint32_t* work, bool count_stats,
                                     int lds_mode, int form, hipStream_t s);
 size_t wavepersist_lds_bytes(const DevScene& sc, int lds_mode);
-// LDS modes 11 / 14 stage the grid image into a static array of this many bytes (ring: 0 none, 1 global
-// records, 2 records in LDS); other modes use dynamic LDS beside the kernel's static words.
-uint32_t wavepersist_grid_cap(int ring);
-// Whether the tail-deferral variant / any variant exists for this (LDS mode, form).
-bool wavepersist_defer_built(int lds_mode, int form);
-bool wavepersist_built(int lds_mode, int form);
+// (wavepersist_grid_cap, wavepersist_defer_built, wavepersist_built: mm_variants.h)
 // Register / scratch / LDS use of the (kStats = false) instance.
 // ring: 0 no tail deferral, 1 rings with global records, 2 rings with records in LDS.
 hipError_t wavepersist_attributes(int lds_mode, int form, int ring, hipFuncAttributes* a);

@@ -1,0 +1,76 @@
+// mm_plan.h — the launch policy of the trace calls as pure functions of scene
+// facts, options and the tile: which query method, which LDS placement, tail
+// deferral and its ring kind, fused resolve, rows per launch.  Plain C++ (no
+// HIP): mm_runtime.hip gathers the inputs and carries the plan out.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "mm_api.h"
+#include "mm_variants.h"
+
+namespace mm {
+
+// Staged samples (tail deferral / no fused resolve) per launch: whole rows up
+// to this many paths (12 B each: 6 GiB).  A multi-frame launch over the cap
+// runs without deferral (fused resolve) or is refused.
+constexpr uint64_t kStagePathsMax = 1ull << 29;
+
+// What mm_upload_scene found out about the scene.
+struct SceneFacts {
+    bool grid_ok = false;    // the certified grid search applies
+    bool grid_slow = false;  // the grid has SLOW records (general rect test)
+    bool grid_wide = false;  // 64-bit cell words with per-face list ranges
+    bool grid_flat = false;  // the maze forms apply (grid_build.h GridHost::flat_ok)
+    bool lean_ok = false;    // no SLOW rect records (loop form 7, grid search)
+    uint32_t n_nodes = 0, n_rects = 0;  // production node array length, rects
+    uint32_t bytes = 0, off_box = 0, off_data = 0;  // the grid image: its size and section offsets
+    const char* grid_why = "";  // why there is no grid
+};
+
+// The options the policy reads (mm_ctx.h opt_*, include/mm_api.h MM_OPT_*).
+struct PlanOptions {
+    int pipe = MM_PIPE_AUTO;
+    int opt_ww = -1;
+    bool opt_lds = true;
+    int opt_lds_rects = 1;
+    bool opt_fuse = true;
+    int opt_persist = 2;
+    int opt_defer = -1;
+    uint32_t opt_defer_min = 1u << 24;
+};
+
+struct Choice {
+    int form = 0, mode = 0;
+    int code = MM_OK;  // else `error` is the text
+    std::string error;
+};
+// The query method for the scene and MM_OPT_TRAVERSAL: a BVH loop form, or the grid form with its slow /
+// wide / flat variants applied.  (The `mode` of the result is unused.)
+Choice choose_method(const SceneFacts& f, const PlanOptions& o);
+// The LDS placement of the wave-persistent kernel for choose_method's form; the form changes where the
+// placement needs another (a grid whose index does not fit LDS: auto takes the BVH).
+Choice choose_placement(const SceneFacts& f, const PlanOptions& o, int form);
+
+// Bytes the placement stages (dynamic LDS, or the static grid array's content).
+inline size_t lds_stage_bytes(const SceneFacts& f, int mode) {
+    return lds_stage_bytes(mode, f.n_nodes, f.n_rects, f.bytes, f.off_data, f.off_box);
+}
+
+struct LaunchPlan {
+    bool defer = false;  // mirror-tail deferral (the tail rings)
+    int ring = 0;        // its ring kind: 1 records in global memory, 2 in LDS
+    bool fuse = false;   // resolve fused into the trace kernel
+    uint32_t rows_per_batch = 0;
+    int code = MM_OK;    // else `error` is the text
+    std::string error;
+};
+constexpr size_t kNotBuilt = ~(size_t)0;
+// static_lds[k - 1]: the static LDS (sharedSizeBytes) of the deferral kernel with ring kind k, or kNotBuilt.
+// multi_fn: null for a single-frame call, else the name of the multi-frame entry point the call came through.
+LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mode, const size_t static_lds[2],
+                     const mm_ext& e, uint32_t w, uint32_t h, uint32_t n_frames, const char* multi_fn);
+
+}  // namespace mm

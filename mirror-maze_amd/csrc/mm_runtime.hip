@@ -23,6 +23,7 @@
 #include "mm_api.h"
 #include "mm_ctx.h"
 #include "mm_launch.h"
+#include "mm_plan.h"
 
 using namespace mm;
 
@@ -32,12 +33,6 @@ size_t build_compact_rects(const mm_rect* rects, uint32_t n_rects, const uint32_
 }
 
 constexpr uint32_t kStatusSlots = 1024;
-constexpr uint32_t kRingDiagWords = 16;  // after the status words: the first timed-out ring wait's record
-constexpr size_t kFailedKept = 64;
-// Staged samples (tail deferral / no fused resolve) per launch: whole rows up
-// to this many paths (12 B each: 6 GiB).  A multi-frame launch over the cap
-// runs without deferral (fused resolve) or is refused.
-constexpr uint64_t kStagePathsMax = 1ull << 29;
 
 namespace {
 
@@ -73,6 +68,24 @@ DevScene dev_scene(const mm_ctx* c) {
     s.n_nodes = c->n_nodes;
     s.n_rects = c->n_rects;
     return s;
+}
+
+// The policy's inputs (mm_plan.h) from the context.
+SceneFacts scene_facts(const mm_ctx* c) {
+    SceneFacts f;
+    f.grid_ok = c->grid_ok; f.grid_slow = c->grid_slow; f.grid_wide = c->grid_wide; f.grid_flat = c->grid_flat;
+    f.lean_ok = c->lean_ok;
+    f.n_nodes = c->n_nodes; f.n_rects = c->n_rects;
+    f.bytes = c->grid.bytes; f.off_box = c->grid.off_box; f.off_data = c->grid.off_data;
+    f.grid_why = c->grid_why.c_str();
+    return f;
+}
+PlanOptions plan_options(const mm_ctx* c) {
+    PlanOptions o;
+    o.pipe = c->pipe; o.opt_ww = c->opt_ww; o.opt_lds = c->opt_lds; o.opt_lds_rects = c->opt_lds_rects;
+    o.opt_fuse = c->opt_fuse; o.opt_persist = c->opt_persist; o.opt_defer = c->opt_defer;
+    o.opt_defer_min = c->opt_defer_min;
+    return o;
 }
 
 void free_scene(mm_ctx* c) {
@@ -210,112 +223,57 @@ int read_aux(mm_ctx* c, mm_stats* st) {
     return MM_OK;
 }
 
-// ---- per-call status (see mm_ctx::h_status) -------------------------------
-uint32_t status_load(const mm_ctx* c, uint64_t launch) {
-    return __atomic_load_n(c->h_status + launch % kStatusSlots, __ATOMIC_ACQUIRE);
-}
+// ---- per-call status (mm_calls.h) -------------------------------------------
+// An earlier call that failed on the GPU is reported first, by name.
+int report_failure(mm_ctx* c, const char* suffix) { return c->calls.report_failure(suffix, c->err); }
 
-// Device address of the status word for the next launch.  A slot still held
-// by a launch kStatusSlots earlier that has not finished is waited for.
-int next_status(mm_ctx* c, uint32_t*& dev_word) {
-    const uint64_t id = c->launch_seq;
-    const uint32_t s = (uint32_t)(id % kStatusSlots);
-    if (c->slot_owner[s] && !(status_load(c, c->slot_owner[s] - 1) & kStatusDone)) {
-        HIPC(c, hipStreamSynchronize(c->stream));
-        if (!(status_load(c, c->slot_owner[s] - 1) & kStatusDone)) HIPC(c, hipDeviceSynchronize());
-        if (!(status_load(c, c->slot_owner[s] - 1) & kStatusDone))
-            return fail(c, MM_ERR_HIP, "status word of an earlier launch never completed");
+// One launch of the open call (CallTracker::begin_call): takes its status slot, runs
+// launch(status word, launch id) -- which enqueues the kernel and returns MM_OK or what fail() gave it --
+// and, unless the kernel publishes its status itself (self_publish: the wave-persistent kernel's last wave
+// does), enqueues the publish of the error flag into the status word.  The slot is taken first (its device
+// address is a kernel argument); if the launch then fails to enqueue, the slot is released as
+// finished-clean, and the call is still tracked for the launches it did enqueue.
+template <typename L>
+int enqueue_launch(mm_ctx* c, bool self_publish, L&& launch) {
+    uint32_t slot = 0;
+    if (int rc = c->calls.next_status(slot, c->err)) return rc;
+    int rc = prof_mark(c);
+    if (!rc) rc = launch(c->d_status + slot, (uint32_t)c->calls.last_launch());
+    if (rc) {
+        c->calls.release_unqueued();
+        return rc;
     }
-    if (c->slot_owner[s]) {  // fold the finished occupant's bits into its call, if still pending
-        const uint64_t prev = c->slot_owner[s] - 1;
-        for (auto& k : c->pending)
-            if (prev >= k.first && prev < k.first + k.n) k.bits |= status_load(c, prev) & ~kStatusDone;
-    }
-    __atomic_store_n(c->h_status + s, 0u, __ATOMIC_RELEASE);
-    c->slot_owner[s] = id + 1;
-    c->launch_seq = id + 1;
-    dev_word = c->d_status + s;
-    return MM_OK;
-}
-
-// The record a timed-out ring wait left (trace_kernels.hip ring_timeout), as
-// text, when it belongs to one of the launches [first, first + n) of the call
-// being reported; consumed then (the device writes a new record only into a
-// consumed one).  A record of an older launch than the call's is stale (its
-// call was reported without it) and is dropped; a newer one is left for its
-// own call.
-std::string ring_diag_text(mm_ctx* c, uint64_t first, uint64_t n) {
-    uint32_t* d = c->h_status + kStatusSlots;
-    if (__atomic_load_n(d, __ATOMIC_ACQUIRE) != 1u) return "";  // none, or being written (2)
-    uint32_t w[kRingDiagWords];
-    for (uint32_t i = 0; i < kRingDiagWords; ++i) w[i] = __atomic_load_n(d + i, __ATOMIC_RELAXED);
-    const uint32_t rel = w[15] - (uint32_t)first;  // launch ids are the context's launch numbers, mod 2^32
-    if (rel >= (uint32_t)n) {
-        if ((int32_t)rel < 0) __atomic_store_n(d, 0u, __ATOMIC_RELEASE);  // stale: free the record
-        return "";
-    }
-    const uint64_t t1 = w[12] | (uint64_t)w[13] << 32;
-    char b[320];
-    snprintf(b, sizeof(b),
-             " [first timed-out wait (launch %u): %s of entry %u (slot %u, lap %u) in block %u wave %u lane %u "
-             "wanted turn %u, saw %u; reserved %u, claimed %u; gave up after %u polls at device clock %llu]",
-             w[15], w[1] == 1 ? "reader" : "writer", w[2], w[2] % kTailRing, w[2] / kTailRing, w[7], w[8], w[9],
-             w[3], w[4], w[5], w[6], w[14], (unsigned long long)t1);
-    __atomic_store_n(d, 0u, __ATOMIC_RELEASE);
-    return b;
-}
-
-std::string error_text(mm_ctx* c, uint32_t bits, uint64_t first, uint64_t n) {
-    std::string s;
-    auto add = [&](const std::string& m) { s += s.empty() ? m : std::string("; ") + m; };
-    if (bits & kErrStack) add("traversal stack overflow (depth > 50)");
-    if (bits & kErrRing) add("tail ring wait timed out (kernel protocol error)" + ring_diag_text(c, first, n));
-    if (bits & kErrInjected) add("injected fault (MM_OPT_FAULT_INJECT)");
-    if (bits & kErrLost) add("injected lost tail-ring entry (MM_OPT_FAULT_INJECT 4)");
-    if (bits & kErrPublish) add("the launch's status could not be published (its error flag was read after a sync)");
-    return s.empty() ? "unknown error" : s;
-}
-int error_code(uint32_t bits) { return (bits & ~kErrStack) ? MM_ERR_HIP : MM_ERR_STACK; }
-
-// Fold finished calls' status words into the failed list (non-blocking).
-void poll_calls(mm_ctx* c) {
-    for (auto it = c->pending.begin(); it != c->pending.end();) {
-        uint32_t bits = it->bits;
-        bool done = true;
-        for (uint64_t l = it->first; l < it->first + it->n && done; ++l) {
-            // a slot reused by a later launch: this launch finished, its bits are in it->bits
-            if (c->slot_owner[l % kStatusSlots] != l + 1) continue;
-            const uint32_t w = status_load(c, l);
-            done = (w & kStatusDone) != 0;
-            bits |= w & ~kStatusDone;
+    if (!self_publish) {
+        uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
+        const hipError_t pe = launch_publish_status(err_dev, c->d_status + slot, c->stream);
+        if (pe != hipSuccess) {
+            // fold the kernel's error flag into THIS launch's slot (after a sync), so it is
+            // never published by -- and blamed on -- a later call's launch
+            uint32_t bits = 0;
+            (void)hipStreamSynchronize(c->stream);
+            (void)hipMemcpy(&bits, err_dev, sizeof(bits), hipMemcpyDeviceToHost);
+            (void)hipMemset(err_dev, 0, sizeof(bits));
+            c->calls.fold_unpublished(bits);
+            return fail(c, MM_ERR_HIP, std::string("launch_publish_status: ") + hipGetErrorString(pe));
         }
-        if (!done) { ++it; continue; }
-        if (bits) {
-            c->failed.push_back({it->id, bits, it->what + " -- " + error_text(c, bits, it->first, it->n), false});
-            if (c->failed.size() > kFailedKept) {
-                c->failed_dropped = std::max(c->failed_dropped, c->failed.front().id);
-                c->failed.pop_front();
-            }
-        }
-        it = c->pending.erase(it);
     }
+    return prof_mark(c);
 }
 
-// "call #N (what) failed on the GPU: why" (Failed::what holds "what -- why").
-std::string failed_text(const mm_ctx::Failed& f) {
-    const size_t k = f.what.find(" -- ");
-    return "call #" + std::to_string(f.id) + " (" + f.what.substr(0, k) + ") failed on the GPU: " +
-           (k == std::string::npos ? std::string("unknown error") : f.what.substr(k + 4));
-}
-
-// The oldest unreported failed call, as this call's return code.
-int report_failure(mm_ctx* c, const char* suffix) {
-    poll_calls(c);
-    for (auto& f : c->failed)
-        if (!f.reported) {
-            f.reported = true;
-            return fail(c, error_code(f.bits), failed_text(f) + suffix);
-        }
+// The view and tile checks shared by the trace calls; `name` prefixes the messages.  e: the sampling
+// parameters of a call that has them (mm_trace_tile*), else null and the call's own mirror limit.
+int check_tile(mm_ctx* c, const char* name, const mm_uniform* u, const mm_ext* e, uint32_t mirror_limit, uint32_t x0,
+               uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride) {
+    auto bad = [&](const char* what) { return fail(c, MM_ERR_INVALID, std::string(name) + ": " + what); };
+    if (!(u->view_w >= 1.0f && u->view_w <= 65536.0f && u->view_h >= 1.0f && u->view_h <= 65536.0f))
+        return bad("bad view size");
+    const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
+    if (w == 0 || h == 0 || y_stride == 0 || (e && (e->spp == 0 || e->spp > 4096)))
+        return bad(e ? "empty tile or bad spp" : "empty tile");
+    // the tail records pack bounces | mirror hits << 16 (trace_kernels.hip tail_store)
+    if ((e && e->bounce_limit > 32767) || mirror_limit > 32767)
+        return bad(e ? "bounce or mirror limit above 32767" : "mirror limit above 32767");
+    if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H) return bad("tile outside the frame");
     return MM_OK;
 }
 
@@ -353,10 +311,12 @@ int mm_create(int device, mm_ctx** out) {
                           hipHostMallocMapped | hipHostMallocCoherent),
             "hipHostMalloc(status)");
     if (rc == MM_OK) chk(hipHostGetDevicePointer((void**)&c->d_status, c->h_status, 0), "hipHostGetDevicePointer");
-    if (rc == MM_OK) {
-        std::memset(c->h_status, 0, (kStatusSlots + kRingDiagWords) * sizeof(uint32_t));
-        c->slot_owner.assign(kStatusSlots, 0);
-    }
+    if (rc == MM_OK)  // (the tracker waits for a status slot's earlier launch: the stream, then the device)
+        c->calls = CallTracker(c->h_status, [c](int level) -> int {
+            if (level == 0) HIPC(c, hipStreamSynchronize(c->stream));
+            else HIPC(c, hipDeviceSynchronize());
+            return MM_OK;
+        }, kStatusSlots);
     if (rc != MM_OK) {
         fprintf(stderr, "mm_create: %s\n", c->err.c_str());
         mm_destroy(c);
@@ -599,28 +559,7 @@ int mm_upload_scene(mm_ctx* c, const mm_rect* rects, uint32_t n_rects, const mm_
     if (grid_ok) {
         HIPC(c, hipMalloc((void**)&c->d_grid, gh.bytes));
         HIPC(c, hipMemcpyAsync(c->d_grid, gh.image.data(), gh.bytes, hipMemcpyHostToDevice, c->stream));
-        for (int a = 0; a < 3; ++a) {
-            dg.mn[a] = gh.mn[a]; dg.mx[a] = gh.mx[a]; dg.cell[a] = gh.cell[a]; dg.inv[a] = gh.inv[a];
-            dg.n[a] = gh.n[a];
-        }
-        dg.n_glob = gh.n_glob;
-        dg.slab = gh.slab ? 1u : 0u;
-        dg.slab_y[0] = gh.slab_y[0];
-        dg.slab_y[1] = gh.slab_y[1];
-        for (int a = 0; a < 3; ++a) {
-            dg.nm1[a] = gh.n[a] - 1;
-            dg.nf[a] = (float)gh.n[a];
-        }
-        for (int i = 0; i < 4; ++i) dg.glob[i] = gh.glob[i];
-        dg.cells = c->d_grid;
-        dg.list = reinterpret_cast<const uint16_t*>(c->d_grid + gh.off_list);
-        dg.recs = reinterpret_cast<const uint4*>(c->d_grid + gh.off_recs);
-        dg.box = reinterpret_cast<const float2*>(c->d_grid + gh.off_box);
-        dg.image = reinterpret_cast<const uint4*>(c->d_grid);
-        dg.off_list = gh.off_list; dg.off_recs = gh.off_recs; dg.off_box = gh.off_box; dg.bytes = gh.bytes;
-        dg.off_class = gh.off_class;  // 0: 32-byte records, no class table
-        dg.off_data = gh.off_data;
-        dg.cls = gh.off_class ? reinterpret_cast<const float4*>(c->d_grid + gh.off_class) : nullptr;
+        dg = dev_grid(gh, c->d_grid);
         c->grid_slow = gh.n_slow > 0;
         c->grid_wide = gh.wide;
         c->grid_flat = gh.flat_ok;
@@ -738,68 +677,6 @@ int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
 
 namespace {
 
-// Loop form and LDS mode of the wave-persistent kernel (trace_kernels.hip).
-// 1024-thread blocks at 8 waves per SIMD -> two blocks per CU -> 80 KB of LDS
-// each.  Auto (MM_OPT_TRAVERSAL -1): the certified grid search when the scene
-// allows it (C3 ...), else the lean BVH loop (form 7) when every rect has a
-// compact record and the nodes + records fit LDS, else form 5 with the nodes
-// in LDS when they fit, else through L1/L2.  MM_OPT_LDS_NODES 0 stages nothing.
-int choose_wavepersist(mm_ctx* c, DevScene& sc, int& form, int& mode) {
-    const size_t budget = 80 * 1024;
-    const bool auto_form = c->opt_ww < 0;
-    form = auto_form ? (c->grid_ok ? kFormGrid : (c->lean_ok ? kFormLean : kFormLeafInterior)) : c->opt_ww;
-    if (form == kFormGrid) {
-        if (!c->grid_ok)
-            return fail(c, MM_ERR_UNSUPPORTED, "grid search unavailable for this scene: " + c->grid_why);
-        if (!c->lean_ok || c->grid_slow) form = kFormGridSlow;  // general rect tests for the SLOW records
-        // maze grids (one cell along y, compact records): only the maze forms read them
-        auto flat = [&](int m) {
-            if (c->grid_flat) {
-                if (form != kFormGrid && form != kFormGridWide)
-                    return fail(c, MM_ERR_UNSUPPORTED, "maze grid with SLOW records");
-                form += kFormGridFlat;
-            }
-            if (!wavepersist_built(m, form))
-                return fail(c, MM_ERR_UNSUPPORTED,
-                            "grid form " + std::to_string(form) + " not built for LDS mode " + std::to_string(m));
-            mode = m;
-            return MM_OK;
-        };
-        // modes 11 / 14 stage into the kernel's static grid array: their images must fit its capacity
-        const size_t cap = wavepersist_grid_cap(0);
-        if (c->grid_wide) {  // built only when the whole image fits that capacity (grid_build.cpp)
-            form += kFormGridWide - kFormGrid;
-            return flat(c->opt_lds && c->grid.bytes <= cap ? 11 : 13);
-        }
-        if (c->opt_lds && c->grid.bytes <= cap) return flat(11);
-        // compact records + class table + index (N=64: ~77 KB), leaf boxes global
-        if (c->opt_lds && c->grid_flat && c->grid.off_box <= cap) return flat(14);
-        if (c->opt_lds && c->grid.off_data <= budget) return flat(12);
-        if (!auto_form || !c->opt_lds) return flat(13);
-        // the index does not fit LDS: auto takes the BVH (nodes in LDS or cached), which is not
-        // measured against the all-global grid
-        form = c->lean_ok ? kFormLean : kFormLeafInterior;
-    }
-    if (form == kFormLean && !c->lean_ok) {
-        if (!auto_form) return fail(c, MM_ERR_UNSUPPORTED, "loop form 7 needs compact records for every rect");
-        form = kFormLeafInterior;
-    }
-    const size_t nodes_b = 2 * (size_t)c->n_nodes * sizeof(float4);
-    const size_t recs_b = 40 * (size_t)c->n_rects;
-    // nodes + records in LDS (lean form 7 or form 5), nodes only (form 5), or nothing
-    if (c->opt_lds && c->opt_lds_rects && nodes_b + recs_b <= budget) {
-        mode = 3;
-    } else {
-        if (form == kFormLean && !auto_form)
-            return fail(c, MM_ERR_UNSUPPORTED,
-                        "loop form 7 needs the BVH nodes + compact records in LDS (its other placements "
-                        "measured slower and were removed, DESIGN.md §4)");
-        form = kFormLeafInterior;
-        mode = (c->opt_lds && nodes_b <= budget) ? 1 : 0;
-    }
-    return MM_OK;
-}
-
 // cams: null, or the n_frames cameras of a camera-sequence launch (mm_trace_tile_cameras; u->cam is then unused)
 int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
                     uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev,
@@ -807,22 +684,13 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     if (!c) return MM_ERR_INVALID;
     // the multi-frame entry point this call came through (its conditions apply to a one-camera sequence too)
     const bool multi = n_frames > 1 || cams;
-    const std::string fn = cams ? "mm_trace_tile_cameras" : "mm_trace_tile_frames";
+    const char* fn = cams ? "mm_trace_tile_cameras" : "mm_trace_tile_frames";
     // an earlier call that failed on the GPU is reported first, by name; this call is then not enqueued
     if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
     if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_tile: no scene uploaded");
     if (!u || !e || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_tile: null argument");
-    if (!(u->view_w >= 1.0f && u->view_w <= 65536.0f && u->view_h >= 1.0f && u->view_h <= 65536.0f))
-        return fail(c, MM_ERR_INVALID, "mm_trace_tile: bad view size");
-    const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
-    if (w == 0 || h == 0 || y_stride == 0 || e->spp == 0 || e->spp > 4096)
-        return fail(c, MM_ERR_INVALID, "mm_trace_tile: empty tile or bad spp");
-    // the tail records pack bounces | mirror hits << 16 (trace_kernels.hip tail_store)
-    if (e->bounce_limit > 32767 || e->mirror_limit > 32767)
-        return fail(c, MM_ERR_INVALID, "mm_trace_tile: bounce or mirror limit above 32767");
-    if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H)
-        return fail(c, MM_ERR_INVALID, "mm_trace_tile: tile outside the frame");
-    if (n_frames == 0) return fail(c, MM_ERR_INVALID, fn + ": no frames");
+    if (int rc0 = check_tile(c, "mm_trace_tile", u, e, e->mirror_limit, x0, y0, w, h, y_stride)) return rc0;
+    if (n_frames == 0) return fail(c, MM_ERR_INVALID, std::string(fn) + ": no frames");
     // MM_EXT_RGBA8: 4-byte RGBA8 pixels (the fused texture-write conversion) instead of float4
     const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
     if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
@@ -834,90 +702,38 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
                                            "-byte aligned");
     HIPC(c, hipSetDevice(c->device));
     const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
-    const uint64_t row_paths = (uint64_t)w * e->spp;
-    const uint64_t tile_paths = row_paths * h;
-    // MM_PIPE_WAVEFRONT: the wave-persistent kernel with mirror-tail deferral (compaction) always on
-    const bool wave = c->pipe == MM_PIPE_WAVEFRONT;
-    const bool persist = c->pipe != MM_PIPE_REFERENCE && (wave || c->opt_persist == 2);
+    const bool persist = c->pipe != MM_PIPE_REFERENCE && (c->pipe == MM_PIPE_WAVEFRONT || c->opt_persist == 2);
     if (!persist && c->pipe != MM_PIPE_REFERENCE) return fail(c, MM_ERR_UNSUPPORTED, kRemoved);
+    // the plan (mm_plan.h): query method and LDS placement, then deferral / ring kind / fused resolve / rows
+    // per launch, given the static LDS of the placement's deferral kernels
+    const SceneFacts facts = scene_facts(c);
+    const PlanOptions opts = plan_options(c);
     int form = 0, mode = 0;
-    DevScene sc = dev_scene(c);
     if (persist) {
-        int rc0 = choose_wavepersist(c, sc, form, mode);
-        if (rc0) return rc0;
+        Choice m = choose_method(facts, opts);
+        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
+        if (m.code != MM_OK) return fail(c, m.code, m.error);
+        form = m.form;
+        mode = m.mode;
     }
-    // mirror-tail deferral (MM_OPT_DEFER): samples staged per path, tails run from block-local rings; built for
-    // the grid search and the lean BVH form with records in LDS (other forms run without it).  Auto: with the
-    // whole search structure in LDS (the maze grid with its leaf boxes, or BVH nodes + compact records) and paths
-    // of >= 8 bounces, on launches of >= MM_OPT_DEFER_MIN paths (C3 20 frames per launch 2.64 vs 2.74 ms/frame,
-    // C4 20.97 vs 21.80, profiles/r03/ab_defer_claims.txt; rank 0 of an 8-way C3 split, 41 M paths per launch,
-    // 0.356 vs 0.362, profiles/r03/emulated_scaling/; the N=64 scene, leaf boxes via L1/L2: 5.23 vs 4.90 without),
-    // or where the samples are staged anyway (64 % spp != 0)
-    const bool defer_on =
-        c->opt_defer > 0 ||
-        (c->opt_defer < 0 && (((mode == 11 || mode == 3) && e->bounce_limit >= 8u) ||
-                              ((mode == 11 || mode == 3 || mode == 14) && 64 % e->spp != 0)));
-    const bool defer_built = persist && wavepersist_defer_built(mode, form);
-    if (wave && !defer_built)
-        return fail(c, MM_ERR_UNSUPPORTED, "MM_PIPE_WAVEFRONT: no tail-deferral kernel for this scene's query "
-                                           "method / LDS placement (grid search, or BVH form 7 with nodes + "
-                                           "records in LDS)");
-    bool defer = defer_built && (defer_on || wave) && (wave || tile_paths * n_frames >= c->opt_defer_min);
-    // the deferral kernel's static LDS (tail ring, claimed queue ranges, and with ring kind 2 the rings'
-    // 32 KB of records) must leave two 1024-thread blocks per CU: the records go to LDS where the
-    // image leaves room (C3: 44 KB + 34 KB), else to global memory; a grid image without room even for the
-    // ring words runs without the rings
-    int ring = 0;
-    if (defer) {
-        const size_t img = wavepersist_lds_bytes(sc, mode);
-        const bool static_grid = mode == 11 || mode == 14;  // the image goes into the kernel's static array
-        for (int kind : {2, 1}) {
-            hipFuncAttributes dattr{};
-            if (wavepersist_attributes(mode, form, kind, &dattr) == hipSuccess &&
-                (static_grid ? img <= wavepersist_grid_cap(kind) : img + dattr.sharedSizeBytes <= 80 * 1024)) {
-                ring = kind;
-                break;
-            }
+    size_t static_lds[2] = {kNotBuilt, kNotBuilt};
+    if (persist && wavepersist_defer_built(mode, form) && (c->opt_defer != 0 || c->pipe == MM_PIPE_WAVEFRONT))
+        for (int kind : {1, 2}) {
+            hipFuncAttributes a{};
+            // (a static-grid placement is fitted to the array's capacity: the kernel's own figure is not read)
+            if (lds_static_grid(mode)) static_lds[kind - 1] = 0;
+            else if (wavepersist_attributes(mode, form, kind, &a) == hipSuccess) static_lds[kind - 1] = a.sharedSizeBytes;
         }
-        if (!ring) {
-            if (wave)
-                return fail(c, MM_ERR_UNSUPPORTED, "MM_PIPE_WAVEFRONT: grid image + tail ring exceed the LDS budget");
-            defer = false;
-        }
-    }
-    const bool fusable = persist && c->opt_fuse && 64 % e->spp == 0;
-    // staging bound: a multi-frame launch stages all its frames at once; past kStagePathsMax it runs without
-    // the rings (fused resolve) if it can
-    if (defer && multi && tile_paths * n_frames > kStagePathsMax && fusable && !wave) defer = false;
-    // wave-persistent kernel with whole pixels per 64-path chunk: resolve fused
-    const bool fuse = fusable && !defer;
-    // Rows per launch: the fused resolve needs no staging (one launch covers up to 2^31 paths, a whole C5
-    // frame); staged samples (tail deferral, or no fused resolve) are bounded by kStagePathsMax per launch
-    // (64 Mi paths without deferral, where the non-persistent kernels' short launches lose nothing)
-    const uint64_t batch_paths = fuse ? (1ull << 31) : defer ? kStagePathsMax : (64ull << 20);
-    const uint32_t rows_per_batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(h, batch_paths / row_paths));
-    if (row_paths * rows_per_batch > 0xFFFFFFFFull) return fail(c, MM_ERR_INVALID, "mm_trace_tile: row too large");
-    if (multi) {
-        // several frames in one launch: the wave-persistent kernel's queue, with the fused resolve or
-        // (tail deferral) samples staged per frame
-        if (!fuse && !defer)
-            return fail(c, MM_ERR_UNSUPPORTED, fn + ": needs the wave-persistent kernel with the "
-                                                    "fused resolve (64 % spp == 0) or tail deferral");
-        if (e->flags & MM_EXT_ACCUMULATE)
-            return fail(c, MM_ERR_INVALID, fn + ": frames of one launch cannot accumulate into one image");
-        const uint64_t queue = ((tile_paths + 63) / 64) * 64 * n_frames;
-        if (queue + (1ull << 24) > 0xFFFFFFFFull)
-            return fail(c, MM_ERR_INVALID, fn + ": more paths than one launch holds (2^32)");
-        if (defer && tile_paths * n_frames > kStagePathsMax)
-            return fail(c, MM_ERR_INVALID, fn + ": the frames' staged samples exceed 6 GiB (2^29 paths) per "
-                                                "launch; use fewer frames per launch");
-        if (rows_per_batch < h) return fail(c, MM_ERR_INVALID, fn + ": tile too large for one launch");
-    }
+    const LaunchPlan plan = plan_tile(facts, opts, form, mode, static_lds, *e, w, h, n_frames, multi ? fn : nullptr);
+    if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
+    const bool defer = plan.defer, fuse = plan.fuse;
+    const uint32_t rows_per_batch = plan.rows_per_batch;
+    const uint64_t row_paths = (uint64_t)w * e->spp;
     int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap,
                                    (size_t)(row_paths * rows_per_batch) * (defer ? n_frames : 1));
     if (rc) return rc;
     TailQueue tq;
-    if (defer && ring == 1 && (rc = tail_queue(c, tq))) return rc;  // (records in LDS: no global ring)
+    if (defer && plan.ring == 1 && (rc = tail_queue(c, tq))) return rc;  // (records in LDS: no global ring)
     const float* cams_dev = nullptr;
     if (cams && (rc = stage_cameras(c, cams, n_frames, cams_dev))) return rc;
     // aux: [0..3] stats (zeroed only when counted), [4] error flag (moved into the launch's status word by
@@ -926,7 +742,8 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
     if ((rc = begin_timing(c))) return rc;
     uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-    const uint64_t call_id = ++c->call_seq, first_launch = c->launch_seq;
+    const DevScene sc = dev_scene(c);
+    c->calls.begin_call();
     uint32_t launches = 0;
     for (uint32_t j0 = 0; j0 < h; j0 += rows_per_batch) {
         TileJob job;
@@ -937,7 +754,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
         job.w = w;
         job.h = std::min(rows_per_batch, h - j0);
         job.y_stride = y_stride;
-        job.view_w = W;
+        job.view_w = (uint32_t)u->view_w;
         job.fuse = fuse ? 1u : 0u;
         job.wave_ts = c->d_wave_ts;
         job.wave_ts_cap = c->wave_ts_cap;
@@ -951,25 +768,19 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
             job.defer_from = 1;
             job.defer_lanes = c->opt_defer > 0 ? (uint32_t)c->opt_defer : 32u;
             job.tail = tq;
-            job.ring_lds = ring == 2 ? 1u : 0u;
+            job.ring_lds = plan.ring == 2 ? 1u : 0u;
         }
-        // The launch's status slot is taken first (its device address is a kernel argument); if the
-        // launch then fails to enqueue, the slot is released as finished-clean (a slot left
-        // owned by a launch that never runs would fail every later call on the context), and the call
-        // is still tracked below for the launches it did enqueue.
-        if ((rc = next_status(c, job.status))) break;
         job.ring_diag = c->d_status + kStatusSlots;
-        job.launch_id = (uint32_t)(c->launch_seq - 1);
-        bool enqueued = false;
-        rc = [&]() -> int {
-            if (int r = prof_mark(c)) return r;
+        rc = enqueue_launch(c, persist, [&](uint32_t* status, uint32_t launch_id) -> int {
+            job.status = status;
+            job.launch_id = launch_id;
             if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
             if (persist) {
                 c->last_form = form >= kFormGrid ? kFormGrid : form;
                 c->last_mode = mode;
                 c->last_kern_mode = mode;
                 c->last_kern_form = form;
-                c->last_kern_ring = defer ? ring : 0;
+                c->last_kern_ring = plan.ring;
                 HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev,
                                                  c->d_work, want_stats, mode, form,
                                                  c->stream));
@@ -979,29 +790,11 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
                 mo.block = c->opt_block ? c->opt_block : 256u;
                 HIPC(c, launch_trace_mega(dev_scene(c), job, c->d_samples, c->d_aux, err_dev, want_stats, mo,
                                           c->stream));
-                enqueued = true;  // the kernel runs: its slot is written by the publish below or here
-                const hipError_t pe = launch_publish_status(err_dev, job.status, c->stream);
-                if (pe != hipSuccess) {
-                    // fold the kernel's error flag into THIS launch's slot (after a sync), so it is
-                    // never published by -- and blamed on -- a later call's launch
-                    uint32_t bits = 0;
-                    (void)hipStreamSynchronize(c->stream);
-                    (void)hipMemcpy(&bits, err_dev, sizeof(bits), hipMemcpyDeviceToHost);
-                    (void)hipMemset(err_dev, 0, sizeof(bits));
-                    __atomic_store_n(c->h_status + (c->launch_seq - 1) % kStatusSlots,
-                                     bits | kErrPublish | kStatusDone, __ATOMIC_RELEASE);
-                    return fail(c, MM_ERR_HIP, std::string("launch_publish_status: ") + hipGetErrorString(pe));
-                }
             }
-            enqueued = true;
-            return prof_mark(c);
-        }();
-        if (!enqueued) {
-            c->h_status[(c->launch_seq - 1) % kStatusSlots] = kStatusDone;  // nothing will write this slot
-            break;
-        }
-        launches += fuse ? 1 : 2;
+            return MM_OK;
+        });
         if (rc) break;
+        launches += fuse ? 1 : 2;
         if (fuse) continue;
         // the frames' staged samples and output slices are contiguous (a multi-frame launch is one
         // row batch), so one resolve over h x n_frames rows covers them all
@@ -1014,13 +807,12 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
         }
     }
     c->last_defer = defer;
-    if (c->launch_seq > first_launch) {  // the launches this call enqueued (all of them unless rc)
-        char what[160];
+    char what[160] = "";
+    if (c->calls.call_has_launches())  // the launches this call enqueued (all of them unless rc)
         snprintf(what, sizeof(what), "%s, frames %u..%u, tile (%u, %u) %ux%u / %u, %u spp",
-                 multi ? fn.c_str() : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0, y0, w, h, y_stride,
+                 multi ? fn : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0, y0, w, h, y_stride,
                  e->spp);
-        c->pending.push_back({call_id, first_launch, c->launch_seq - first_launch, what, 0u});
-    }
+    c->calls.end_call(what);
     if (rc) return rc;
     if ((rc = end_timing(c, launches))) return rc;
     if (want_stats) {
@@ -1052,67 +844,39 @@ int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams,
 
 namespace {
 
-// Query policy of mm_query_rays / mm_trace_aov (aov_kernels.hip): the method choose_wavepersist would take
-// for the scene and MM_OPT_TRAVERSAL, without its LDS placements -- those kernels read the scene from global
-// memory, where every grid form and both BVH forms exist.
+// Query policy of mm_query_rays / mm_trace_aov (aov_kernels.hip): the method the trace calls would take for
+// the scene and MM_OPT_TRAVERSAL (mm_plan.h choose_method), without their LDS placements -- those kernels
+// read the scene from global memory, where every grid form and both BVH forms exist.
 int aov_policy(mm_ctx* c, int& policy) {
     if (c->pipe == MM_PIPE_REFERENCE) {
         policy = kAovRef;
         return MM_OK;
     }
-    const bool auto_form = c->opt_ww < 0;
-    const int form = auto_form ? (c->grid_ok ? kFormGrid : (c->lean_ok ? kFormLean : kFormLeafInterior)) : c->opt_ww;
-    if (form == kFormGrid) {
-        if (!c->grid_ok)
-            return fail(c, MM_ERR_UNSUPPORTED, "grid search unavailable for this scene: " + c->grid_why);
-        const bool slow = !c->lean_ok || c->grid_slow;  // general rect tests for the SLOW records
-        if (c->grid_flat && slow) return fail(c, MM_ERR_UNSUPPORTED, "maze grid with SLOW records");
-        policy = kAovGrid + (slow ? kAovGridSlow : 0) + (c->grid_wide ? kAovGridWide : 0) +
-                 (c->grid_flat ? kAovGridFlat : 0);
-    } else if (form == kFormLean) {
-        if (!c->lean_ok && !auto_form)
-            return fail(c, MM_ERR_UNSUPPORTED, "loop form 7 needs compact records for every rect");
-        policy = c->lean_ok ? kAovBvhLean : kAovBvhLi;
-    } else {
-        policy = kAovBvhLi;
-    }
+    const Choice m = choose_method(scene_facts(c), plan_options(c));
+    if (m.code != MM_OK) return fail(c, m.code, m.error);
+    if (grid_form(m.form))
+        policy = kAovGrid + (grid_slow(m.form) ? kAovGridSlow : 0) + (grid_wide(m.form) ? kAovGridWide : 0) +
+                 (grid_flat(m.form) ? kAovGridFlat : 0);
+    else
+        policy = m.form == kFormLean ? kAovBvhLean : kAovBvhLi;
     if (!aov_policy_built(policy))
         return fail(c, MM_ERR_UNSUPPORTED, "query policy " + std::to_string(policy) + " not built");
     return MM_OK;
 }
 
-// One numbered call of one kernel launch + the publish of its error flag into the call's status word
-// (trace_tile_impl's protocol for a non-persistent kernel).  launch(err_dev) enqueues the kernel.
+// One numbered call of one kernel launch (a non-persistent kernel: its error flag is published into the
+// call's status word by a launch of its own).  launch(err_dev) enqueues the kernel.
 extern "C++" template <typename L>
 int enqueue_query_call(mm_ctx* c, const std::string& what, const char* name, L&& launch) {
     int rc = begin_timing(c);
     if (rc) return rc;
-    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-    const uint64_t call_id = ++c->call_seq, first_launch = c->launch_seq;
-    uint32_t* status = nullptr;
-    if ((rc = next_status(c, status))) return rc;
-    if ((rc = prof_mark(c))) {
-        c->h_status[first_launch % kStatusSlots] = kStatusDone;  // nothing will write this slot
-        return rc;
-    }
-    const hipError_t le = launch(err_dev);
-    if (le != hipSuccess) {
-        c->h_status[first_launch % kStatusSlots] = kStatusDone;
-        return fail(c, MM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(le));
-    }
-    c->pending.push_back({call_id, first_launch, 1, what, 0u});
-    const hipError_t pe = launch_publish_status(err_dev, status, c->stream);
-    if (pe != hipSuccess) {
-        // fold the kernel's error flag into this launch's slot after a sync (trace_tile_impl)
-        uint32_t bits = 0;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipMemcpy(&bits, err_dev, sizeof(bits), hipMemcpyDeviceToHost);
-        (void)hipMemset(err_dev, 0, sizeof(bits));
-        __atomic_store_n(c->h_status + first_launch % kStatusSlots, bits | kErrPublish | kStatusDone,
-                         __ATOMIC_RELEASE);
-        return fail(c, MM_ERR_HIP, std::string("launch_publish_status: ") + hipGetErrorString(pe));
-    }
-    if ((rc = prof_mark(c))) return rc;
+    c->calls.begin_call();
+    rc = enqueue_launch(c, false, [&](uint32_t*, uint32_t) -> int {
+        const hipError_t le = launch(reinterpret_cast<uint32_t*>(c->d_aux + 4));
+        return le == hipSuccess ? MM_OK : fail(c, MM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(le));
+    });
+    c->calls.end_call(what);
+    if (rc) return rc;
     return end_timing(c, 2);
 }
 
@@ -1148,13 +912,7 @@ int mm_trace_aov(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, uint32_t
     if (!out->normal_depth && !out->albedo && !out->id) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no output");
     if (n_frames == 0) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no frames");
     if (!cams && n_frames > 1) return fail(c, MM_ERR_INVALID, "mm_trace_aov: several frames need their cameras");
-    if (!(u->view_w >= 1.0f && u->view_w <= 65536.0f && u->view_h >= 1.0f && u->view_h <= 65536.0f))
-        return fail(c, MM_ERR_INVALID, "mm_trace_aov: bad view size");
-    const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
-    if (w == 0 || h == 0 || y_stride == 0) return fail(c, MM_ERR_INVALID, "mm_trace_aov: empty tile");
-    if (mirror_limit > 32767) return fail(c, MM_ERR_INVALID, "mm_trace_aov: mirror limit above 32767");
-    if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H)
-        return fail(c, MM_ERR_INVALID, "mm_trace_aov: tile outside the frame");
+    if (int rc0 = check_tile(c, "mm_trace_aov", u, nullptr, mirror_limit, x0, y0, w, h, y_stride)) return rc0;
     if (reinterpret_cast<uintptr_t>(out->normal_depth) % 16 || reinterpret_cast<uintptr_t>(out->albedo) % 16 ||
         reinterpret_cast<uintptr_t>(out->id) % 4)
         return fail(c, MM_ERR_INVALID, "mm_trace_aov: float4 outputs not 16-byte or id not 4-byte aligned");
@@ -1194,27 +952,13 @@ int mm_sync(mm_ctx* c) {
 
 int mm_last_call(const mm_ctx* c, uint64_t* call_id) {
     if (!c || !call_id) return MM_ERR_INVALID;
-    *call_id = c->call_seq;
+    *call_id = c->calls.last_call();
     return MM_OK;
 }
 
 int mm_call_status(mm_ctx* c, uint64_t call_id) {
     if (!c) return MM_ERR_INVALID;
-    if (call_id == 0 || call_id > c->call_seq) return fail(c, MM_ERR_INVALID, "mm_call_status: no such call");
-    poll_calls(c);
-    for (const auto& k : c->pending)
-        if (k.id == call_id) return MM_PENDING;
-    for (auto& f : c->failed)
-        if (f.id == call_id) {
-            f.reported = true;
-            return fail(c, error_code(f.bits), failed_text(f));
-        }
-    // a finished call not in the failed list: clean -- unless failed calls as old as it were dropped from the list
-    if (call_id <= c->failed_dropped)
-        return fail(c, MM_ERR_INVALID, "mm_call_status: status of call #" + std::to_string(call_id) +
-                                           " no longer kept (older than the last " + std::to_string(kFailedKept) +
-                                           " failed calls)");
-    return MM_OK;
+    return c->calls.call_status(call_id, c->err);
 }
 
 int mm_set_profiling(mm_ctx* c, int enable) {

@@ -387,11 +387,7 @@ constexpr uint32_t kClaimTail = MM_CLAIM_TAIL;  // single claims for the last kC
 // chunk per claim (259,200 chunks in 2.95 ms; profiles/r03/ab_claim_chunks.txt).
 // The wave's claimed range [next, end) lives in LDS, not in registers held
 // across the bounce loop (SGPR pressure there spills into VGPR lanes).
-#ifdef MM_TAIL_CLOCKS
-constexpr uint32_t kClaimWords = 16;
-#else
-constexpr uint32_t kClaimWords = 2;
-#endif
+// (kClaimWords words per wave: mm_variants.h)
 __device__ __forceinline__ uint32_t* claim_words() {
     // (next, end) per wave of a <= 1024-thread block; diagnostics build MM_TAIL_CLOCKS: then the wall clock
     // at the start of the wave's current chunk (lo, hi), its longest chunk so far (10 ns units), its chunks
@@ -727,17 +723,7 @@ __device__ __forceinline__ uint32_t wavepersist_ring_body(const DevScene& sc, co
 // another wave's VALU op in a quad-cycle -- scripts/isa_dual.hip,
 // DESIGN.md s10.)  Each instance's array takes what the block's 80 KB leave
 // after its other static LDS (two 1024-thread blocks per CU).
-constexpr uint32_t kLdsPerBlock = 80 * 1024;
-template <int kRing>
-constexpr uint32_t grid_lds_cap() {
-    uint32_t other = kClaimWords * 16u * 4u + 64u;  // claimed queue ranges + alignment slack
-    if (kRing != 0) other += (4u + kTailRing) * 4u;  // ring counters and turn words
-    if (kRing == 2) other += 4u * kTailRing * 16u;   // ring payload
-#ifdef MM_LANE_STATS
-    other += 2u * kLpCount * 4u;
-#endif
-    return (kLdsPerBlock - other) & ~15u;
-}
+// (kLdsPerBlock, grid_lds_cap<kRing>(): mm_variants.h)
 template <uint32_t kBytes>
 __device__ __forceinline__ uint4* grid_lds() {
     __shared__ uint4 g[kBytes / 16u];
@@ -947,19 +933,8 @@ __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersis
     persistent_exit(job, chunks, t_entry, work, err);
 }
 
-uint32_t wavepersist_grid_cap(int ring) {
-    return ring == 2 ? grid_lds_cap<2>() : ring == 1 ? grid_lds_cap<1>() : grid_lds_cap<0>();
-}
-
 size_t wavepersist_lds_bytes(const DevScene& sc, int lds_mode) {
-    switch (lds_mode) {
-        case 11: return sc.grid.bytes;
-        case 12: return sc.grid.off_data;
-        case 14: return sc.grid.off_box;
-        case 1: return 2 * (size_t)sc.n_nodes * sizeof(float4);
-        case 3: return 2 * (size_t)sc.n_nodes * sizeof(float4) + 5 * (size_t)sc.n_rects * sizeof(uint2);
-        default: return 0;
-    }
+    return lds_stage_bytes(lds_mode, sc.n_nodes, sc.n_rects, sc.grid.bytes, sc.grid.off_data, sc.grid.off_box);
 }
 
 // Resident grid of a persistent kernel: blocks per CU from the occupancy API x
@@ -979,11 +954,11 @@ template <int kLds, int kForm, int kRing>
 static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, Sample* samples,
                                        unsigned long long* stats, uint32_t* err, uint32_t* work, bool count_stats,
                                        hipStream_t s) {
-    // modes 11 / 14 stage into the kernel's static grid array (stage_and_run): no dynamic LDS, and an image
-    // larger than the array is refused here (the host picks the ring kind so that it fits)
-    if ((kLds == 11 || kLds == 14) && wavepersist_lds_bytes(sc, kLds) > grid_lds_cap<kRing>())
+    // the static-grid placements stage into the kernel's static grid array (stage_and_run): no dynamic LDS, and
+    // an image larger than the array is refused here (the host picks the ring kind so that it fits)
+    if (lds_static_grid(kLds) && wavepersist_lds_bytes(sc, kLds) > grid_lds_cap<kRing>())
         return hipErrorInvalidValue;
-    const size_t lds = (kLds == 11 || kLds == 14) ? 0 : wavepersist_lds_bytes(sc, kLds);
+    const size_t lds = lds_static_grid(kLds) ? 0 : wavepersist_lds_bytes(sc, kLds);
     auto kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing>
                             : k_trace_wavepersist<false, kLds, kForm, kRing>;
     if (job.cams)
@@ -997,41 +972,7 @@ static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, S
     return hipGetLastError();
 }
 
-// (LDS mode, form) pairs; the tail-deferral variant (MM_OPT_DEFER) is built
-// for the grid search and the lean BVH form with records in LDS.  The build
-// holds what MM_PIPE_AUTO can select: the grid search, and the BVH forms for
-// scenes the grid cannot take (nodes + records in LDS, nodes only, nothing).
-// (The A/B-only placements -- split node cache, nodes with global records,
-// dictionary nodes, loop form 0 -- measured slower and were removed in round
-// 6)  The maze forms (flat grid walk,
-// compact records; grid_build.cpp decides) in every grid placement: a maze
-// grid's compact records are read by no other form.  (No SLOW records in
-// maze grids: no slow maze forms.)
-#define MM_FLAT_INSTANCES(X)                                                                                  \
-    X(11, kFormGridWide + kFormGridFlat) X(11, kFormGrid + kFormGridFlat) X(14, kFormGrid + kFormGridFlat)     \
-    X(12, kFormGrid + kFormGridFlat) X(13, kFormGridWide + kFormGridFlat) X(13, kFormGrid + kFormGridFlat)
-#define MM_DEFER_INSTANCES(X)                                                                                 \
-    X(11, kFormGrid) X(12, kFormGrid) X(13, kFormGrid)                                                        \
-    X(11, kFormGridSlow) X(12, kFormGridSlow) X(13, kFormGridSlow)                                            \
-    X(11, kFormGridWide) X(13, kFormGridWide) X(11, kFormGridWideSlow) X(13, kFormGridWideSlow)               \
-    MM_FLAT_INSTANCES(X) X(3, kFormLean)
-#define MM_WP_INSTANCES(X)                                                                                    \
-    MM_DEFER_INSTANCES(X) X(0, kFormLeafInterior) X(1, kFormLeafInterior) X(3, kFormLeafInterior)
-
-bool wavepersist_built(int lds_mode, int form) {
-#define MM_WP(L, F) if (lds_mode == L && form == F) return true;
-    MM_WP_INSTANCES(MM_WP)
-#undef MM_WP
-    return false;
-}
-
-bool wavepersist_defer_built(int lds_mode, int form) {
-#define MM_WP(L, F) if (lds_mode == L && form == F) return true;
-    MM_DEFER_INSTANCES(MM_WP)
-#undef MM_WP
-    return false;
-}
-
+// The built (LDS mode, form) pairs: mm_variants.h.
 hipError_t launch_trace_wavepersist(const DevScene& sc, const TileJob& job, Sample* samples,
                                     unsigned long long* stats, uint32_t* err, uint32_t* work, bool count_stats,
                                     int lds_mode, int form, hipStream_t s) {
