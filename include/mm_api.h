@@ -310,7 +310,10 @@ int  mm_set_option(mm_ctx* ctx, int key, int value);
  *   MM_INFO_LAST_SCRATCH     its private (scratch) bytes per lane: VGPR spills + traversal stack
  *   MM_INFO_LAST_STATIC_LDS  its static LDS bytes per block (the tail ring's words)
  *   MM_INFO_GRID_LDS_CAP     bytes the grid placements 11 / 14 stage into (their static LDS array without
- *                            tail rings; the grid builder's budget: no grid image is built larger) */
+ *                            tail rings; the grid builder's budget: no grid image is built larger)
+ *   MM_INFO_GRID_FLAT        1 if the grid takes the maze forms (one y cell, compact 16-byte records + class table)
+ *   MM_INFO_GRID_SLAB        1 if the two global rects are a floor / ceiling pair, sorted by y, a query tests one of
+ *   MM_INFO_GRID_CLASSES     threshold classes of the compact records (0 without them) */
 #define MM_INFO_GRID_OK          1
 #define MM_INFO_GRID_CELLS_X     2
 #define MM_INFO_GRID_CELLS_Y     3
@@ -329,6 +332,9 @@ int  mm_set_option(mm_ctx* ctx, int key, int value);
 #define MM_INFO_LAST_SCRATCH     16
 #define MM_INFO_LAST_STATIC_LDS  17
 #define MM_INFO_GRID_LDS_CAP     18
+#define MM_INFO_GRID_FLAT        19
+#define MM_INFO_GRID_SLAB        20
+#define MM_INFO_GRID_CLASSES     21
 int  mm_scene_info(const mm_ctx* ctx, int key, double* value);
 
 /* Diagnostics: record, for every wave of the wave-persistent kernel, four u64

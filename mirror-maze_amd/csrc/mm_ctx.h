@@ -37,6 +37,7 @@ struct mm_ctx {
     bool grid_slow = false;  // the grid has SLOW records (general rect test)
     bool grid_wide = false;  // 64-bit cell words with per-face list ranges
     bool grid_flat = false;  // the flat forms apply (grid_build.h GridHost::flat_ok)
+    uint32_t grid_classes = 0;  // threshold classes of its compact records (GridHost::n_class; MM_INFO_GRID_CLASSES)
     std::string grid_why;
     uint32_t* d_idx = nullptr;
     uint32_t n_rects = 0, n_nodes = 0;

@@ -93,7 +93,7 @@ void free_scene(mm_ctx* c) {
     (void)hipFree(c->d_shade); (void)hipFree(c->d_idx); (void)hipFree(c->d_recs);
     (void)hipFree(c->d_grid);
     c->d_grid = nullptr; c->grid = DevGrid{}; c->grid_ok = false; c->grid_slow = false; c->grid_wide = false;
-    c->grid_flat = false;
+    c->grid_flat = false; c->grid_classes = 0;
     c->d_rects = nullptr; c->d_nodes = nullptr; c->d_nodes_ref = nullptr; c->d_geo = nullptr; c->d_recs = nullptr; c->d_shade = nullptr; c->d_idx = nullptr;
     c->has_scene = false;
 }
@@ -456,6 +456,9 @@ int mm_scene_info(const mm_ctx* c, int key, double* value) {
         case MM_INFO_GRID_FACES: *value = c->grid_ok && c->grid_wide ? 1.0 : 0.0; return MM_OK;
         case MM_INFO_LAST_DEFER: *value = c->last_defer ? 1.0 : 0.0; return MM_OK;
         case MM_INFO_GRID_LDS_CAP: *value = wavepersist_grid_cap(0); return MM_OK;
+        case MM_INFO_GRID_FLAT: *value = c->grid_ok && c->grid_flat ? 1.0 : 0.0; return MM_OK;
+        case MM_INFO_GRID_SLAB: *value = c->grid_ok && g.slab && g.slab_y[0] < g.slab_y[1] ? 1.0 : 0.0; return MM_OK;
+        case MM_INFO_GRID_CLASSES: *value = c->grid_ok ? c->grid_classes : 0u; return MM_OK;
         case MM_INFO_LAST_VGPRS:
         case MM_INFO_LAST_SCRATCH:
         case MM_INFO_LAST_STATIC_LDS: {
@@ -563,6 +566,7 @@ int mm_upload_scene(mm_ctx* c, const mm_rect* rects, uint32_t n_rects, const mm_
         c->grid_slow = gh.n_slow > 0;
         c->grid_wide = gh.wide;
         c->grid_flat = gh.flat_ok;
+        c->grid_classes = gh.n_class;
     }
     HIPC(c, hipMemcpyAsync(c->d_shade, shade.data(), shade.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(c->d_idx, idx, n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));

@@ -25,7 +25,7 @@ import aov_support as A
 MM_OPT_LDS_NODES, MM_OPT_TRAVERSAL, MM_OPT_DEFER, MM_OPT_DEFER_MIN = 1, 7, 21, 22
 MM_OPT_GRID_CELL, MM_OPT_GRID_WIDE = 25, 26
 MM_INFO_GRID_OK, MM_INFO_GRID_CELLS_X, MM_INFO_GRID_CELLS_Y, MM_INFO_GRID_CELLS_Z = 1, 2, 3, 4
-MM_INFO_GRID_FACES = 13
+MM_INFO_GRID_FACES, MM_INFO_GRID_FLAT = 13, 19
 
 PITCH = 8.0      # the crate's lattice (placement 1 and 3; 2^-3 in placement 2)
 HALF = 64.0      # its half-width

@@ -80,9 +80,10 @@ def _check_grid(r, name, cell=100):
 
 
 def _form(r, name):
-    """(walk, cell words) of the uploaded grid: the maze forms have one cell
-    along y (on a maze: grid_build.cpp's flat_ok); FACES: 64-bit cell words."""
-    maze = name.startswith("maze") and r.scene_info(S.MM_INFO_GRID_CELLS_Y) == 1.0
+    """(walk, cell words) of the uploaded grid: MM_INFO_GRID_FLAT is grid_build.cpp's
+    flat_ok, the maze forms (one cell along y follows); FACES: 64-bit cell words."""
+    maze = r.scene_info(S.MM_INFO_GRID_FLAT) == 1.0
+    assert not maze or r.scene_info(S.MM_INFO_GRID_CELLS_Y) == 1.0, name
     return ("maze" if maze else "3-D", "wide" if r.scene_info(S.MM_INFO_GRID_FACES) == 1.0 else "plain")
 
 
