@@ -44,7 +44,10 @@ struct Ray {
 // walk, both only under ray_fast_ok -- |d| in [2^-40, 2^40] on every axis.
 // There one fma Newton step on the hardware v_rcp_f32 gives RN(1/d) exactly
 // (scripts/verify_fast_rsq.hip checks every float of either sign in
-// [2^-44, 2^44]); outside, the value is never used.
+// [2^-44, 2^44]); outside, the value -- inf or NaN for d = +-0, for a denormal
+// (the hardware reciprocal flushes it) and for +-inf -- is never used:
+// tests/test_gpu_guard_edges.py sends such rays through every query form and
+// compares the answers with the reference walk's, bit for bit.
 __device__ __forceinline__ float rcp_guarded(float d) {
     const float y = __builtin_amdgcn_rcpf(d);
     const float e = __builtin_fmaf(-d, y, 1.0f);
@@ -107,7 +110,13 @@ __device__ __forceinline__ bool ray_fast_ok_boxed(const Ray& r) {
     return ok;
 }
 
-// RN(a / d) given y = RN(1/d), inside the guarded ranges.
+// RN(a / d) given y = RN(1/d), inside the guarded ranges -- up to the sign of a
+// zero: for a = -0 and d > 0 it returns +0 where IEEE gives -0 (r adds zeros of
+// opposite signs, +0, and fma(+0, y, -0) = +0 for y > 0).  No caller can tell:
+// every quotient is compared (slab times through fminf / fmaxf and ordered
+// compares, d1 / d2 against 0 and the extent), and a hit distance is stored
+// only when a > 0.1.  scripts/verify_fast_rsq.hip checks both statements on
+// the device (ieee_div_markstein, markstein_zero).
 __device__ __forceinline__ float qdiv(float a, float d, float y) {
     const float q = a * y;
     const float r = __builtin_fmaf(-q, d, a);
