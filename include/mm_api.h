@@ -209,6 +209,55 @@ int  mm_trace_aov(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams, uin
                   uint32_t mirror_limit, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                   uint32_t y_stride, const mm_aov* out);
 
+/* ---- denoising a traced frame ------------------------------------------------
+ * An edge-aware a-trous filter over throughput-mode frames, guided by the
+ * buffers of mm_trace_aov over the same tile and cameras: (id, mirror hits,
+ * side) names the surface a pixel shows, also when it is seen in a mirror, so
+ * a tap is taken only from the same surface; a depth term and a luminance term
+ * weigh the taps that are.  (The reference hides its noise with the display
+ * blur, mm_present, which smears across every edge.)
+ *
+ * color_dev: n_frames*w*h float4 (16-byte aligned), what mm_trace_tile /
+ * _frames / _cameras write: element f*w*h + j*w + i.  guides: the three
+ * buffers of one mm_trace_aov call, all required.  out_dev: n_frames*w*h
+ * float4 (16-byte aligned); with MM_DN_RGBA8 4-byte pixels (4-byte aligned):
+ * the texture-write conversion (mm_quantize_rgba8's) of the last pass's float
+ * result.  The filter works in tile index space: neighbours are tile
+ * neighbours, whatever y_stride the tile was traced with, and never another
+ * frame's pixels.
+ *
+ * All arithmetic is IEEE binary32, no contraction, in the order written.
+ * hk[5] = {1/16, 1/4, 3/8, 1/4, 1/16}; C is the pass's input (color_dev for
+ * pass 0, else the previous pass's output); nd, al, id the guides (the same
+ * for every pass); for pass i: s = 1 << i, sl = sigma_l * (1.0f / (float)s);
+ * lum(q) = (0.25f*C_q.r + 0.5f*C_q.g) + 0.25f*C_q.b.  For pixel p = (x, y):
+ *   S = (0,0,0); W = 0
+ *   for dy = -2..2 (outer), dx = -2..2 (inner):
+ *     q = (x + s*dx, y + s*dy); skip q outside [0,w) x [0,h)
+ *     unless dx == 0 && dy == 0, skip q unless
+ *       id_q == id_p (all 32 bits)  and  al_q.w == al_p.w  and
+ *       (nd_p.x*nd_q.x + nd_p.y*nd_q.y) + nd_p.z*nd_q.z >= 0
+ *     g = hk[dy+2] * hk[dx+2]
+ *     if sigma_z > 0: t = (nd_p.w - nd_q.w) / (sigma_z * (nd_p.w + nd_q.w)); g = g / (1.0f + t*t)
+ *     if sigma_l > 0: t = (lum(p) - lum(q)) / sl;                            g = g / (1.0f + t*t)
+ *     S.c = S.c + g * C_q.c  (c = r, g, b);  W = W + g
+ *   out.rgb = S / W;  out.a = C_p.a
+ * (the centre tap always counts, so W > 0; defined for finite colours and
+ * nd.w > 0, which the trace and AOV calls produce).
+ *
+ * MM_ERR_INVALID: a null context, p, input, guide or output; n_passes outside
+ * 1..MM_DENOISE_MAX_PASSES; unknown flags; w, h or n_frames 0; a misaligned
+ * pointer; out_dev overlapping color_dev or a guide; w*h over 2^31 - 1 or more
+ * than 2^40 pixels in all.  Enqueued on the context's stream like
+ * mm_quantize_rgba8; the inputs are never written.  The intermediate images
+ * are context-owned scratch that grows on demand (growing waits for the
+ * device once, as the camera staging does); its reuse is ordered on the
+ * stream -- and by an event when the stream was changed in between -- so
+ * back-to-back calls never wait on the host. */
+int  mm_denoise_frames(mm_ctx* ctx, const float* color_dev, const mm_aov* guides,
+                       const mm_denoise_params* p, uint32_t n_frames,
+                       uint32_t w, uint32_t h, void* out_dev);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

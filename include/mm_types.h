@@ -98,6 +98,17 @@ typedef struct mm_aov {
 #define MM_AOV_ID_MIRROR_END 0x80000000u  /* | k: a mirror's front, mirror_limit reached */
 #define MM_AOV_ID_RECT       0x00FFFFFFu  /* mask of k                          */
 
+/* Parameters of mm_denoise_frames (mm_api.h): the edge-aware a-trous filter
+ * over a traced frame, guided by the mm_aov buffers of the same tile. */
+#define MM_DENOISE_MAX_PASSES 8
+#define MM_DN_RGBA8 1u   /* the output is RGBA8 (4 B per pixel), not float4   */
+typedef struct mm_denoise_params {   /* 16 bytes */
+    uint32_t n_passes;  /* 1..MM_DENOISE_MAX_PASSES; pass i spaces its taps 2^i apart */
+    float    sigma_z;   /* depth term; <= 0: off */
+    float    sigma_l;   /* luminance term of pass 0, halved every pass; <= 0: off */
+    uint32_t flags;     /* MM_DN_RGBA8 */
+} mm_denoise_params;
+
 /* Return codes (0 = success; never panics or throws across the ABI). */
 #define MM_OK               0
 #define MM_ERR_INVALID     -1  /* bad argument / shape                        */

@@ -1,0 +1,242 @@
+// denoise_kernels.hip — the edge-aware a-trous filter of mm_denoise_frames
+// (include/mm_api.h states the arithmetic; tests/denoise_ref.c restates it in
+// plain C and the GPU result equals it bit for bit).
+//
+//   k_denoise_keys  once per call: (id, al.w) of every pixel as one 8-byte
+//                   record, so a tap's key test reads 8 B in one load instead
+//                   of 4 B + a 4-byte word out of a 16-byte stride (measured:
+//                   0.41 against 0.50 ms per frame of four passes).
+//   k_denoise_pass  one pass: one thread per output pixel, 64 x 4 blocks, so a
+//                   wave is a 64-pixel row segment and each of its 25 taps is
+//                   one coalesced row segment of the input (taps 2^pass apart).
+//                   The taps are accumulated one after the other in the order
+//                   of the specification (dy outer, dx inner): no tree, no
+//                   contraction (-ffp-contract=off).  The last pass may store
+//                   RGBA8 (unorm8 of its float result, as k_quantize).
+//
+// A taken tap is four divisions (two soft terms, a quotient and a weight each),
+// and 25 taps of the compiler's IEEE sequence (~12 operations per division)
+// made the pass VALU-bound at 0.143 ms per 1080p pass (profiles/denoise/ab.txt).
+// So a pixel is computed twice over, if need be:
+//   fast   straight-line code, no branch: tap addresses are clamped into the
+//          frame, so every load is unconditional and in bounds, and a tap
+//          row's 15 loads are issued ahead of its arithmetic; a tap outside
+//          the frame or rejected by the key test is computed and not added
+//          (a select, not a zero weight: the accumulators never see it).
+//          Quotients are Markstein's over a correctly rounded reciprocal
+//          (dn_div below, 6 operations), which are RN(a / d) inside exponent
+//          ranges that a taken tap's operands leave only for odd inputs.
+//   exact  where some taken tap of the pixel was outside those ranges, the
+//          pixel is computed again by a plain loop with IEEE division, and
+//          that result is stored.
+#include <hip/hip_runtime.h>
+
+#include "mm_launch.h"
+#include "mm_trace.h"
+
+namespace mm {
+
+namespace {
+
+__device__ __forceinline__ float dn_lum(const float4& c) { return (0.25f * c.x + 0.5f * c.y) + 0.25f * c.z; }
+
+__global__ void k_denoise_keys(const float4* __restrict__ al, const uint32_t* __restrict__ id,
+                               uint2* __restrict__ keys, size_t n) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+        keys[i] = make_uint2(id[i], __float_as_uint(al[i].w));
+}
+
+// The key of pixel i: (id, al.w).  Two keys are equal when the ids are (all 32 bits) and the al.w are as floats.
+__device__ __forceinline__ void dn_key(const DnPass& a, uint32_t i, uint32_t& id, float& mh) {
+    const uint2 k = a.keys[i];
+    id = k.x;
+    mh = __uint_as_float(k.y);
+}
+
+// RN(a / d) without the compiler's IEEE division sequence: Markstein's quotient over y = RN(1/d) (mm_trace.h
+// qdiv, rcp_guarded: 6 operations instead of ~12).  It is the correctly rounded quotient when nothing under- or
+// overflows on the way.  The conditions used here, with room to spare:
+//   dn_den_ok  |d| in [2^-40, 2^40]          (rcp_guarded's verified range is [2^-44, 2^44]);
+//   dn_num_ok  a = 0 or |a| in [2^-60, 2^60];
+// then |a / d| lies in [2^-100, 2^100] and the exact residual a - q*d, whose lowest bit is above 2^-48 |a|, is a
+// normal float.  A NaN fails either test.  A zero numerator gives a zero (its sign may differ from IEEE's; both
+// quotients t below are used as t * t only) or, over a denominator whose reciprocal is not finite, a NaN, which
+// the test of 1 + t*t then catches.  The weights g need no test: they start as 2^-8 .. 9/64 and are divided at
+// most twice by an f in [1, 2^40].
+__device__ __forceinline__ bool dn_den_ok(float d) {
+    bool ok = fabsf(d) >= 0x1p-40f;
+    ok &= fabsf(d) <= 0x1p40f;
+    return ok;
+}
+__device__ __forceinline__ bool dn_num_ok(float a) {
+    bool ok = fabsf(a) >= 0x1p-60f;
+    ok &= fabsf(a) <= 0x1p60f;
+    ok |= a == 0.0f;
+    return ok;
+}
+__device__ __forceinline__ float dn_div(float a, float d) { return qdiv(a, d, rcp_guarded(d)); }
+
+struct DnPixel {
+    float4 C, nd;   // the centre's colour and (normal, distance)
+    uint32_t id;    // its key
+    float mh;
+    float lum;
+    uint32_t x, y;  // in the frame (w * h < 2^31: mm_denoise_frames)
+};
+
+// Whether tap q shows the centre's surface (the three-clause test of the specification).
+__device__ __forceinline__ bool dn_same_surface(const DnPass& a, const DnPixel& c, uint32_t q, const float4& ndq) {
+    uint32_t idq;
+    float mhq;
+    dn_key(a, q, idq, mhq);
+    const float d = (c.nd.x * ndq.x + c.nd.y * ndq.y) + c.nd.z * ndq.z;
+    bool same = idq == c.id;
+    same &= mhq == c.mh;
+    same &= d >= 0.0f;
+    return same;
+}
+
+// kZ / kL: the depth / luminance term is on (sigma > 0).
+// The fast form: returns false if a taken tap left the guarded quotients' ranges (o is then not to be used).
+template <bool kZ, bool kL>
+__device__ __forceinline__ bool dn_pixel_fast(const DnPass& a, const DnPixel& c, float4& o) {
+    // 1 / sl for the luminance quotients; sl is the same for every tap of the pass
+    const float ysl = kL ? rcp_guarded(a.sl) : 0.0f;
+    const bool sl_ok = dn_den_ok(a.sl);
+    constexpr float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float Sx = 0.0f, Sy = 0.0f, Sz = 0.0f, W = 0.0f;
+    uint32_t bad = 0;  // (a VGPR, so that it can go through the barriers below with the sums)
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        // (unsigned: a coordinate below 0 wraps to above 2^32 - 257, one past the frame stays below 2^31 + 256)
+        // (the row's addresses hang on cx, cy, which the compiler cannot see through: it would otherwise work
+        // out all 75 of the pixel, 150 VGPRs, ahead of the first row)
+        uint32_t cx = c.x, cy = c.y;
+        asm volatile("" : "+v"(cx), "+v"(cy));
+        const uint32_t qy = cy + a.s * (uint32_t)dy;
+        const bool in_y = qy < a.h;
+        const uint32_t row = (in_y ? qy : cy) * a.w;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const uint32_t qx = cx + a.s * (uint32_t)dx;
+            const bool in_x = qx < a.w;
+            const uint32_t q = row + (in_x ? qx : cx);  // clamped: always a pixel of this frame
+            const float4 Cq = a.in[q];
+            const float4 ndq = a.nd[q];
+            bool take = in_x & in_y;
+            if (dx != 0 || dy != 0) take &= dn_same_surface(a, c, q, ndq);
+            float g = hk[dy + 2] * hk[dx + 2];
+            bool ok = true;
+            if constexpr (kZ) {
+                const float az = c.nd.w - ndq.w, dz = a.sigma_z * (c.nd.w + ndq.w);
+                bool ok_z = dn_den_ok(dz);
+                ok_z &= dn_num_ok(az);
+                ok_z |= az == 0.0f;
+                ok &= ok_z;
+                const float t = dn_div(az, dz);
+                const float f = 1.0f + t * t;
+                ok &= f <= 0x1p40f;
+                g = dn_div(g, f);
+            }
+            if constexpr (kL) {
+                const float al = c.lum - dn_lum(Cq);
+                ok &= sl_ok & dn_num_ok(al);
+                const float t = qdiv(al, a.sl, ysl);
+                const float f = 1.0f + t * t;
+                ok &= f <= 0x1p40f;
+                g = dn_div(g, f);
+            }
+            bad |= (uint32_t)(take & !ok);
+            const float nx = Sx + g * Cq.x, ny = Sy + g * Cq.y, nz = Sz + g * Cq.z, nw = W + g;
+            Sx = take ? nx : Sx;
+            Sy = take ? ny : Sy;
+            Sz = take ? nz : Sz;
+            W = take ? nw : W;
+        }
+        // a row's 15 loads may be batched ahead of its arithmetic, not all 75 of the pixel (one basic block is
+        // otherwise laid out loads first: 260 VGPRs, or spills under an occupancy bound): the next row's loads
+        // stay behind this point, and this row's sums and range tests are done before it
+        asm volatile("" : "+v"(Sx), "+v"(Sy), "+v"(Sz), "+v"(W), "+v"(bad) : : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    o = make_float4(Sx / W, Sy / W, Sz / W, c.C.w);
+    return bad == 0;
+}
+
+// The exact form: the specification as it is written, IEEE division, a rolled loop (it runs for few pixels).
+template <bool kZ, bool kL>
+__device__ __forceinline__ void dn_pixel_exact(const DnPass& a, const DnPixel& c, float4& o) {
+    float Sx = 0.0f, Sy = 0.0f, Sz = 0.0f, W = 0.0f;
+#pragma nounroll
+    for (int i = 0; i < 25; ++i) {
+        const int dy = i / 5 - 2, dx = i % 5 - 2;
+        const uint32_t qx = c.x + a.s * (uint32_t)dx, qy = c.y + a.s * (uint32_t)dy;
+        if (qx >= a.w || qy >= a.h) continue;
+        const uint32_t q = qy * a.w + qx;
+        const float4 ndq = a.nd[q];
+        if (i != 12 && !dn_same_surface(a, c, q, ndq)) continue;
+        const float4 Cq = a.in[q];
+        const float ky = dy == 0 ? 3.0f / 8.0f : (dy == 1 || dy == -1 ? 1.0f / 4.0f : 1.0f / 16.0f);
+        const float kx = dx == 0 ? 3.0f / 8.0f : (dx == 1 || dx == -1 ? 1.0f / 4.0f : 1.0f / 16.0f);
+        float g = ky * kx;
+        if constexpr (kZ) {
+            const float t = (c.nd.w - ndq.w) / (a.sigma_z * (c.nd.w + ndq.w));
+            g = g / (1.0f + t * t);
+        }
+        if constexpr (kL) {
+            const float t = (c.lum - dn_lum(Cq)) / a.sl;
+            g = g / (1.0f + t * t);
+        }
+        Sx = Sx + g * Cq.x;
+        Sy = Sy + g * Cq.y;
+        Sz = Sz + g * Cq.z;
+        W = W + g;
+    }
+    o = make_float4(Sx / W, Sy / W, Sz / W, c.C.w);
+}
+
+template <bool kZ, bool kL>
+__global__ __launch_bounds__(256) void k_denoise_pass(const DnPass a) {
+    const uint32_t ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+    DnPixel c;
+    c.x = tx * 64 + threadIdx.x;  // (tiles_x * 64 < w + 64 <= 2^31 + 63)
+    c.y = ty * 4 + threadIdx.y;
+    if (c.x >= a.w || c.y >= a.h) return;
+    const uint32_t p = c.y * a.w + c.x;
+    c.C = a.in[p];
+    c.nd = a.nd[p];
+    dn_key(a, p, c.id, c.mh);
+    c.lum = dn_lum(c.C);
+    float4 o;
+    if (!dn_pixel_fast<kZ, kL>(a, c, o)) dn_pixel_exact<kZ, kL>(a, c, o);
+    if (a.rgba8)
+        reinterpret_cast<uint32_t*>(a.out)[p] =
+            unorm8(o.x) | (unorm8(o.y) << 8) | (unorm8(o.z) << 16) | (unorm8(o.w) << 24);
+    else
+        reinterpret_cast<float4*>(a.out)[p] = o;
+}
+
+}  // namespace
+
+hipError_t launch_denoise_keys(const float4* al, const uint32_t* id, uint2* keys, size_t n, hipStream_t s) {
+    const size_t blocks = std::min<size_t>((n + 255) / 256, 1u << 20);
+    hipLaunchKernelGGL(k_denoise_keys, dim3((unsigned)blocks), dim3(256), 0, s, al, id, keys, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_pass(const DnPass& pass, hipStream_t s) {
+    DnPass a = pass;
+    a.tiles_x = (a.w + 63) / 64;
+    const uint64_t tiles = (uint64_t)a.tiles_x * ((a.h + 3) / 4);
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)tiles), block(64, 4);
+    const bool z = a.sigma_z > 0.0f, l = a.sigma_l > 0.0f;
+    if (z && l) hipLaunchKernelGGL((k_denoise_pass<true, true>), grid, block, 0, s, a);
+    else if (z) hipLaunchKernelGGL((k_denoise_pass<true, false>), grid, block, 0, s, a);
+    else if (l) hipLaunchKernelGGL((k_denoise_pass<false, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_denoise_pass<false, false>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace mm

@@ -65,6 +65,17 @@ struct mm_ctx {
     float* h_cams = nullptr;
     float* d_cams = nullptr;
     size_t cams_cap = 0, cams_next = 0;
+    // mm_denoise_frames' scratch: the two intermediate images a frame's passes alternate between (one frame
+    // each, `dn_img_cap` pixels in all) and the call's packed key records (`dn_keys_cap`).  A call's kernels are
+    // ordered after the last call's on the same stream; `dn_done` (recorded after every call) orders them when
+    // the stream changed.
+    float4* d_dn_img = nullptr;
+    size_t dn_img_cap = 0;
+    uint2* d_dn_keys = nullptr;
+    size_t dn_keys_cap = 0;
+    hipEvent_t dn_done = nullptr;
+    hipStream_t dn_stream = nullptr;
+    bool dn_pending = false;
     // aux: stats[4] (u64) + error flag (u32)
     unsigned long long* d_aux = nullptr;
     uint32_t* d_work = nullptr;  // the wave-persistent kernel's self-cleaning queue heads + waves-done word (4 KB)

@@ -131,6 +131,20 @@ hipError_t launch_chunk_packets(const float4* fb, const uint32_t* chunks, uint32
                                 float4* out, hipStream_t s);
 hipError_t launch_quantize(const float4* in, uint32_t* out, size_t n, hipStream_t s);
 
+// One pass of mm_denoise_frames over one frame (denoise_kernels.hip); every pointer points at that frame.
+struct DnPass {
+    const float4* in = nullptr;      // the pass's input image
+    const float4* nd = nullptr;      // guide: normal_depth
+    const uint2* keys = nullptr;     // guide: the packed (id, bits of albedo.w) records of launch_denoise_keys
+    void* out = nullptr;             // float4 per pixel, or RGBA8 (4 B) when rgba8 is set
+    uint32_t w = 0, h = 0, tiles_x = 0;  // w * h < 2^31; tiles_x: set by the launcher
+    uint32_t s = 1;                  // tap spacing, 1 << pass
+    float sigma_z = 0.0f, sigma_l = 0.0f, sl = 0.0f;  // sl = sigma_l * (1.0f / (float)s)
+    uint32_t rgba8 = 0;
+};
+hipError_t launch_denoise_keys(const float4* al, const uint32_t* id, uint2* keys, size_t n, hipStream_t s);
+hipError_t launch_denoise_pass(const DnPass& pass, hipStream_t s);
+
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);
 

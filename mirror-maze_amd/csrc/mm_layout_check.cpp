@@ -25,5 +25,8 @@ static_assert(sizeof(mm_ext) == 24, "mm_ext is 24 B");
 static_assert(sizeof(mm_stats) == 32, "mm_stats is 32 B");
 static_assert(sizeof(mm_aov) == 24 && offsetof(mm_aov, albedo) == 8 && offsetof(mm_aov, id) == 16,
               "mm_aov is three pointers");
+static_assert(sizeof(mm_denoise_params) == 16 && offsetof(mm_denoise_params, sigma_z) == 4 &&
+                  offsetof(mm_denoise_params, flags) == 12,
+              "mm_denoise_params is four 4-byte fields");
 
 extern "C" int mm_layout_ok(void) { return 1; }

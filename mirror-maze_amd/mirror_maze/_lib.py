@@ -50,6 +50,7 @@ MM_OWN_STREAM = C.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF).value  # (void*)-1
 MM_COMM_ID_BYTES, MM_GATHER_SELF_VIA_RCCL = 128, 1
 MM_AOV_ID_MISS, MM_AOV_ID_FAILED, MM_AOV_ID_RECT = 0xFFFFFFFF, 0xFFFFFFFE, 0x00FFFFFF
 MM_AOV_ID_SURFACE, MM_AOV_ID_MIRROR_END = 0x40000000, 0x80000000
+MM_DENOISE_MAX_PASSES, MM_DN_RGBA8 = 8, 1
 
 
 class mm_rect(C.Structure):
@@ -82,6 +83,10 @@ class mm_stats(C.Structure):
 
 class mm_aov(C.Structure):
     _fields_ = [("normal_depth", C.c_void_p), ("albedo", C.c_void_p), ("id", C.c_void_p)]
+
+
+class mm_denoise_params(C.Structure):
+    _fields_ = [("n_passes", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("flags", C.c_uint32)]
 
 
 class mm_rng(C.Structure):
@@ -125,6 +130,8 @@ EXPORTS = {
     "mm_query_rays": (C.c_int, [P, P, C.c_uint64, P]),
     "mm_trace_aov": (C.c_int, [P, C.POINTER(mm_uniform), P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mm_aov)]),
+    "mm_denoise_frames": (C.c_int, [P, P, C.POINTER(mm_aov), C.POINTER(mm_denoise_params), C.c_uint32, C.c_uint32,
+                                    C.c_uint32, P]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

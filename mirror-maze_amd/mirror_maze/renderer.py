@@ -305,6 +305,49 @@ class Renderer:
                                        C.byref(a)))
         return bufs
 
+    def denoise(self, color, aov, n_passes: int = 4, sigma_z: float = 0.02, sigma_l: float = 0.5,
+                rgba8: bool = False, out=None):
+        """Edge-aware a-trous denoise of traced frames (mm_denoise_frames).
+        `color`: an (h, w, 4) or (n, h, w, 4) float32 CUDA tensor, what
+        trace_tile / trace_tile_frames / trace_tile_cameras return; `aov`: the
+        dict trace_aov returns for the same tile and cameras (all three
+        buffers).  Pass i spaces its 5x5 taps 2^i apart; a tap counts only
+        where it shows the centre's surface, weighed by a depth term (sigma_z)
+        and a luminance term (sigma_l, halved every pass); a sigma <= 0 turns
+        its term off.  Returns a float32 tensor of color's shape (`out` if
+        given), or with rgba8 / a uint8 `out` its RGBA8 conversion (equal to
+        quantize() of the float result).  The inputs are not written."""
+        import torch
+
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+                and color.dim() in (3, 4) and color.shape[-1] == 4):
+            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
+        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        if not (isinstance(aov, dict) and all(k in aov for k in self.AOV_NAMES)):
+            raise ValueError(f"aov must hold the buffers {self.AOV_NAMES} of trace_aov")
+        for k in self.AOV_NAMES:
+            shape, dt = ((n, h, w), torch.int32) if k == "id" else ((n, h, w, 4), torch.float32)
+            t = aov[k]
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == color.device and t.dtype == dt
+                    and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"aov[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {color.device}")
+        if not 1 <= int(n_passes) <= _lib.MM_DENOISE_MAX_PASSES:
+            raise ValueError(f"n_passes must be 1..{_lib.MM_DENOISE_MAX_PASSES}")
+        if out is None:
+            out = torch.empty(color.shape, dtype=torch.uint8 if rgba8 else torch.float32, device=color.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
+                  and out.dtype in (torch.float32, torch.uint8) and out.shape == color.shape
+                  and not (rgba8 and out.dtype != torch.uint8)):
+            raise ValueError("out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
+        r8 = out.dtype == torch.uint8
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        a = _lib.mm_aov(*[aov[k].data_ptr() for k in self.AOV_NAMES])
+        p = _lib.mm_denoise_params(int(n_passes), float(sigma_z), float(sigma_l), _lib.MM_DN_RGBA8 if r8 else 0)
+        self._check(lib().mm_denoise_frames(self._ctx, color.data_ptr(), C.byref(a), C.byref(p), n, w, h,
+                                            out.data_ptr()))
+        return out
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the

@@ -10,12 +10,19 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 32 --frames 40 --batch 20 --out flythrough/
     python scripts/flythrough.py --maze 10 --frames 30 --no-render     # the camera path only: no GPU
     python scripts/flythrough.py --maze 32 --frames 40 --aov aov/       # + feature buffers per frame
+    python scripts/flythrough.py --maze 32 --frames 40 --denoise        # + frame_NNNN_dn.png beside each frame
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
 distance along the mirror chain, 1e30 where nothing is hit) and id.npy (uint32
 rect index | kind << 30) through Renderer.trace_aov (mm_trace_aov, --mirrors as
 its mirror limit): the inputs a denoiser or a compositor takes beside the frame.
+
+--denoise also writes frame_NNNN_dn.png beside each frame: the frame through
+Renderer.denoise (mm_denoise_frames, its default passes and sigmas), guided by
+the batch's feature buffers -- traced for it if --aov did not ask for them.  The
+batch is then traced as float frames; frame_NNNN.png is their RGBA8 conversion,
+the same bytes as without --denoise.
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -56,6 +63,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="flythrough", help="folder for frame_NNNN.png")
     ap.add_argument("--aov", metavar="DIR", default=None,
                     help="also write per-frame feature buffers: DIR/frame_NNNN/{normal.png,depth.npy,id.npy}")
+    ap.add_argument("--denoise", action="store_true",
+                    help="also write frame_NNNN_dn.png: the frame through Renderer.denoise, guided by its feature buffers")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
@@ -86,16 +95,25 @@ def main(argv=None) -> int:
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
-            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=True)
+            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not a.denoise)
+            frames = (r.quantize(img) if a.denoise else img).cpu().numpy()
             r.sync()
-            frames = img.cpu().numpy()
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
             print(f"# frames {f0}..{f0 + len(batch) - 1}: one launch, {out_dir}/frame_{f0:04d}.png ...", flush=True)
+            if a.aov is None and not a.denoise:
+                continue
+            bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
+                               want=Renderer.AOV_NAMES if a.denoise else ("normal_depth", "id"))
+            if a.denoise:
+                clean = r.denoise(img, bufs, rgba8=True).cpu().numpy()
+                r.sync()
+                for k in range(len(batch)):
+                    write_png(out_dir / f"frame_{f0 + k:04d}_dn.png", clean[k])
+                print(f"# frames {f0}..{f0 + len(batch) - 1}: denoised, {out_dir}/frame_{f0:04d}_dn.png ...", flush=True)
+            r.sync()
             if a.aov is None:
                 continue
-            bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height, want=("normal_depth", "id"))
-            r.sync()
             nd = bufs["normal_depth"].cpu().numpy()
             ids = bufs["id"].cpu().numpy().view(np.uint32)
             for k in range(len(batch)):
