@@ -14,8 +14,10 @@
 // with exact unit normals (SLOW records) are listed too; the kernel runs the
 // general ray_rect_intersect on them (grid_rect<kSlow>).
 // Per rect the image also holds its grid record (mm_grid.h: grid_rect; made
-// from rect_compact.cpp's record, built with identity slots) and the box of
-// the reference BVH leaf holding it -- the box the certificate tests.
+// from rect_compact.cpp's record, built with identity slots) and the inner
+// window of the box of the reference BVH leaf holding it -- what the fast
+// certificate tests; the boxes themselves, which the full certificate tests,
+// are kept beside the image (GridHost::boxes).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -508,7 +510,40 @@ bool build_grid(const mm_rect* rects, uint32_t n_rects, const mm_node* nodes, ui
             std::memcpy(&box[6 * (size_t)k], b, sizeof b);
         }
     }
-    std::memcpy(&g.image[g.off_box], box.data(), 24u * (size_t)n_rects);
+    // The fast certificate's inner windows (mm_grid.h) take the boxes' place in the image -- same offset,
+    // same 24 B per rect, so the image's size and the launch plan's facts are what they were -- and the
+    // boxes become cold data behind it.  A window is (centre c, half-width h) per axis, tested as
+    // |RN(p - c)| <= h: on the rect's normal axis k everything (h = inf), provided the rect's plane lies in
+    // the box's k range; on the other two axes it lies inside [mn + m, mx - m], m = 2^-20 C, with h shortened
+    // by 2^-22 h for the rounding of p - c.  A rect without a FAST record, in no leaf, or whose plane lies
+    // outside its leaf's k range gets empty windows (h = -1): its hits always take the full certificate.
+    g.win_m = (float)std::ldexp(C, -20);
+    g.omax = (float)(8.0 * C);
+    std::vector<float> win(6 * (size_t)n_rects);
+    for (uint32_t k = 0; k < n_rects; ++k) {
+        const float* b = &box[6 * (size_t)k];
+        float* w = &win[6 * (size_t)k];
+        const uint32_t meta = grecs[8 * (size_t)k + 7], ak = (meta >> 20) & 3u;
+        float ok;
+        std::memcpy(&ok, &grecs[8 * (size_t)k], 4);
+        const bool covered = (meta >> 30) == 0u && ak < 3u && b[2 * ak] <= ok && ok <= b[2 * ak + 1];
+        for (uint32_t a = 0; a < 3; ++a) {
+            float c = 0.0f, h = -1.0f;
+            if (covered && a == ak) {
+                h = INFINITY;
+            } else if (covered) {
+                const double xl = (double)b[2 * a] + (double)g.win_m, xh = (double)b[2 * a + 1] - (double)g.win_m;
+                c = (float)(0.5 * (xl + xh));
+                const double hd = std::min((double)c - xl, xh - (double)c) * (1.0 - 0x1p-22);
+                h = (float)hd;
+                if ((double)h > hd) h = std::nextafterf(h, -INFINITY);
+            }
+            w[2 * a] = c;
+            w[2 * a + 1] = h;
+        }
+    }
+    std::memcpy(&g.image[g.off_box], win.data(), 24u * (size_t)n_rects);
+    g.boxes = std::move(box);
     return true;
 }
 

@@ -39,6 +39,13 @@ struct GridHost {
     // precedes their records, so a kernel that stages the data first finds the table at LDS address 0 and
     // record k at kGridClassBytes + 16 k -- compile-time offsets), else the records.
     uint32_t off_data = 0;
+    // The section at off_box holds each rect's inner window (3 x (centre, half-width): its reference leaf's
+    // box shrunk by win_m on the in-plane axes, unbounded on the normal axis, empty for a rect the fast
+    // certificate does not cover; mm_grid.h).  The leaf boxes themselves, which only the full certificate reads, are
+    // cold data outside the image: 3 x (mn, mx) per rect, uploaded behind it.
+    float win_m = 0.0f;  // 2^-20 C
+    float omax = 0.0f;   // 8 C: the largest |origin coordinate| the fast certificate covers
+    std::vector<float> boxes;
     std::vector<uint8_t> image;
 };
 

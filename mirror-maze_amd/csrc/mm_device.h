@@ -60,7 +60,8 @@ __host__ __device__ constexpr bool grid_wide(int f) { return grid_base(f) >= kFo
 // Shade record: s0 = (color.rgb, is_mirror), s1 = emission (rgba).
 // Uniform grid of the certified search (mm_grid.h, built by grid_build.cpp).
 // The device image is one buffer: [cells: n_cells u64][list: u16, padded to
-// 16 B][recs: 2 x uint4 per rect][box: 3 x float2 per rect]; the byte
+// 16 B][recs: 2 x uint4 per rect][box: 3 x float2 per rect: the inner windows];
+// the leaf boxes (3 x float2 per rect) follow the image in the same allocation; the byte
 // offsets of the sections let a kernel stage it in LDS (all of it, records
 // first, or the cells + lists prefix).
 struct DevGrid {
@@ -72,7 +73,9 @@ struct DevGrid {
     const void* cells;         // per cell: list base, count (and per-face ranges when wide; mm_grid.h)
     const uint16_t* list;      // rect indices
     const uint4* recs;         // per-rect grid records (grid_build.cpp; mm_grid.h: grid_rect)
-    const float2* box;         // per rect: its reference leaf's box, (mn, mx) per axis
+    const float2* box;         // per rect: its inner window, (centre, half-width) per axis (mm_grid.h: the fast certificate)
+    const float2* cbox;        // per rect: its reference leaf's box, (mn, mx) per axis (cold: behind the image)
+    float omax;                // the fast certificate covers origins with |o| <= omax = 8 C on every axis
     const uint4* image;        // the whole image (16-B units)
     uint32_t off_list, off_recs, off_box, bytes;  // section offsets in bytes
     // Compact records (maze grids, grid_build.cpp): 16 B per rect -- o_k, o_v,
@@ -109,6 +112,8 @@ inline DevGrid dev_grid(const GridHost& gh, const uint8_t* image_dev) {
     dg.list = reinterpret_cast<const uint16_t*>(image_dev + gh.off_list);
     dg.recs = reinterpret_cast<const uint4*>(image_dev + gh.off_recs);
     dg.box = reinterpret_cast<const float2*>(image_dev + gh.off_box);
+    dg.cbox = reinterpret_cast<const float2*>(image_dev + gh.bytes);
+    dg.omax = gh.omax;
     dg.image = reinterpret_cast<const uint4*>(image_dev);
     dg.off_list = gh.off_list; dg.off_recs = gh.off_recs; dg.off_box = gh.off_box; dg.bytes = gh.bytes;
     dg.off_class = gh.off_class;  // 0: 32-byte records, no class table

@@ -49,6 +49,55 @@
 // rect twice never changes (best, bk, tie) (same a, same k), so skipping the
 // repeat changes nothing.
 //
+// The fast certificate.  The leaf-box check costs six quotients, and the
+// result almost never needs them: the hit point lies on R*, and R* lies in
+// L*'s box B, so the check can fail only for a hit within rounding of B's
+// faces.  For a = best > 0.1 it is enough that, on every axis, a lies between
+// the two slab quotients q(B_lo), q(B_hi), q(b) = qdiv(RN(b - o), d, y): then
+// tmin <= a <= tmax, hence tmax >= tmin, tmax > 0 and tmin <= best.  Under the
+// guards qdiv(n, d, y) = RN(n / d) (mm_trace.h) -- and where the quotient is
+// too small for that theorem, |n / d| < 2^-10, qdiv's three operations keep
+// its magnitude below 4 |n / d| + 2^-148 < 0.1 < a, which orders it against a
+// as the true quotient would be -- so q is monotone in b, rising or falling
+// with the sign of d.
+//   * Normal axis k of R* (a FAST record): a = qdiv(RN(r_k - o_k), d_k, y_k)
+//     is q(r_k), the same three operations on the record's plane coordinate,
+//     so B_k,lo <= r_k <= B_k,hi puts a between q(B_k,lo) and q(B_k,hi).
+//     grid_build.cpp checks that per rect; the device does nothing.
+//   * An in-plane axis v.  If n_lo <= a d_v <= n_hi as real numbers, with
+//     n_lo = RN(B_lo - o_v), n_hi = RN(B_hi - o_v), then dividing by d_v and
+//     rounding (RN is monotone, RN(a) = a) puts a between the two quotients,
+//     whatever the sign of d_v.  The device computes p = RN(o_v + a d_v), one
+//     fma, and tests |RN(p - c)| <= h for the rect's inner window (c, h) on
+//     that axis.  grid_build.cpp chooses c and h so that
+//     [c - h (1 + 2^-23), c + h (1 + 2^-23)] lies inside
+//     [B_lo + m, B_hi - m], m = 2^-20 C (C as in eps): p - c is off by at
+//     most 2^-24 of itself (a subtraction that underflows is exact), so a p
+//     that passes has B_lo + m <= p <= B_hi - m, and |p| <= C.  With
+//     x = o_v + a d_v exactly, |x - p| <= u |p| <= u C (u = 2^-24; a
+//     denormal p is off by 2^-150), so
+//         a d_v = x - o_v >= (B_lo - o_v) + m - u C,
+//     while n_lo <= (B_lo - o_v) + u |B_lo - o_v| <= (B_lo - o_v) + u (C + |o_v|).
+//     Hence n_lo <= a d_v once m >= u (2 C + |o_v|), and the same from above
+//     for n_hi.  Nothing bounds |o_v| by itself -- a telephoto camera's bounce
+//     origins are rounded at ulp(D) and may lie anywhere (mm_path.h) -- so the
+//     fast path also tests max |o| <= omax = 8 C: then u (2 C + |o_v|) <=
+//     10 u C < 16 u C = m.  No bound on a is needed: a d_v enters p inside
+//     the fma, unrounded.  (The window's bounds are computed in double from
+//     B_lo + m, B_hi - m; their rounding, 2^-52 relative, is far inside the
+//     6 u C to spare.)
+// The windows take the boxes' place in the image (24 B per rect: (c, h) per
+// axis, h = inf on the normal axis, h = -1 -- never passed -- for a rect with
+// no FAST record, in no leaf, or whose plane lies outside its leaf's range);
+// the boxes are cold data behind the image, read from global memory by the
+// lanes whose fast test fails, which then run the six quotients as before.
+// scripts/grid_sim.c CERTFAST=1 replays both certificates on every query of a
+// C3 frame and of the N=64 scene: 137.0 M and 262.3 M fast-accepted, none of
+// which fails the full one; 0.09 % and 0.23 % of the 64-query waves hold a
+// lane on the full certificate (profiles/cert_fast/grid_sim_certfast.txt).
+// tests/test_cert_fast.py checks "fast => full" on a C statement of both for
+// rays aimed at the band around the rects' edges.
+//
 // A tie, a failed leaf-box check or a ray outside the Markstein guards /
 // the grid runs the reference walk (the BVH traversal) instead.
 #pragma once
@@ -174,7 +223,7 @@ struct GridView {
     CellsT cells;  // per cell: a 64-bit (wide) or 32-bit word (list range): LdsCells or GlobalCells
     ListT list;    // rect indices (u16): LdsList or GlobalList
     RecsT recs;    // 2 x uint4 per rect, or 1 (compact records)
-    BoxT box;      // 3 x float2 per rect: its reference leaf's (mn, mx) per axis
+    BoxT box;      // 3 x float2 per rect: its inner window, (centre, half-width) per axis (the leaf boxes: g.cbox)
     ClsT cls;      // compact records' threshold classes (float4), else unused
 };
 template <typename C, typename L, typename R, typename B, typename K>
@@ -572,21 +621,34 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
     }
     if (tie) return false;
     MM_LANE_STAT(kLpCert);
-    // certificate: R*'s reference leaf box passes at every t > best
-    // (compact grids: the box of rect k = e / 8 at byte 24 k = 3 e, two pairable adds)
-    const float2* bp = kFlat ? reinterpret_cast<const float2*>(reinterpret_cast<const char*>(gv.box) + (bk + twice(bk)))
+    // fast certificate (header): the hit point, rounded once, inside R*'s inner
+    // window on every axis, from an origin within omax
+    // (compact grids: the window of rect k = e / 8 at byte 24 k = 3 e, two pairable adds)
+    const float2* wp = kFlat ? reinterpret_cast<const float2*>(reinterpret_cast<const char*>(gv.box) + (bk + twice(bk)))
                              : gv.box + 3 * bk;
     bk = rect_index<kFlat>(bk);
-    const float2 bxx = bp[0], byy = bp[1], bzz = bp[2];
-    const float tx1 = qdiv(bxx.x - r.o.x, r.d.x, r.y.x), tx2 = qdiv(bxx.y - r.o.x, r.d.x, r.y.x);
-    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
-    const float ty1 = qdiv(byy.x - r.o.y, r.d.y, r.y.y), ty2 = qdiv(byy.y - r.o.y, r.d.y, r.y.y);
-    tmin = fmaxf(tmin, fminf(ty1, ty2));
-    tmax = fminf(tmax, fmaxf(ty1, ty2));
-    const float tz1 = qdiv(bzz.x - r.o.z, r.d.z, r.y.z), tz2 = qdiv(bzz.y - r.o.z, r.d.z, r.y.z);
-    tmin = fmaxf(tmin, fminf(tz1, tz2));
-    tmax = fminf(tmax, fmaxf(tz1, tz2));
-    if (!(tmax >= tmin && tmax > 0.0f && tmin <= best)) return false;
+    const float2 wx = wp[0], wy = wp[1], wz = wp[2];
+    const float px = __builtin_fmaf(best, r.d.x, r.o.x), py = __builtin_fmaf(best, r.d.y, r.o.y),
+                pz = __builtin_fmaf(best, r.d.z, r.o.z);
+    bool clear = fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z)) <= g.omax;
+    clear &= fabsf(px - wx.x) <= wx.y;
+    clear &= fabsf(py - wy.x) <= wy.y;
+    clear &= fabsf(pz - wz.x) <= wz.y;
+    if (!clear) {
+        // full certificate: R*'s reference leaf box passes at every t > best
+        MM_LANE_STAT(kLpCertFull);
+        const float2* bp = g.cbox + 3 * bk;
+        const float2 bxx = bp[0], byy = bp[1], bzz = bp[2];
+        const float tx1 = qdiv(bxx.x - r.o.x, r.d.x, r.y.x), tx2 = qdiv(bxx.y - r.o.x, r.d.x, r.y.x);
+        float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
+        const float ty1 = qdiv(byy.x - r.o.y, r.d.y, r.y.y), ty2 = qdiv(byy.y - r.o.y, r.d.y, r.y.y);
+        tmin = fmaxf(tmin, fminf(ty1, ty2));
+        tmax = fminf(tmax, fmaxf(ty1, ty2));
+        const float tz1 = qdiv(bzz.x - r.o.z, r.d.z, r.y.z), tz2 = qdiv(bzz.y - r.o.z, r.d.z, r.y.z);
+        tmin = fmaxf(tmin, fminf(tz1, tz2));
+        tmax = fminf(tmax, fmaxf(tz1, tz2));
+        if (!(tmax >= tmin && tmax > 0.0f && tmin <= best)) return false;
+    }
     t = best;
     index = bk;
     return true;

@@ -577,8 +577,11 @@ int mm_upload_scene(mm_ctx* c, const mm_rect* rects, uint32_t n_rects, const mm_
     if (!fast) gwhy = "scene coordinates outside the exact-division guards";
     DevGrid dg{};
     if (grid_ok) {
-        HIPC(c, hipMalloc((void**)&c->d_grid, gh.bytes));
+        // the image, then the leaf boxes (cold: only the full certificate reads them, mm_grid.h)
+        const size_t box_bytes = gh.boxes.size() * sizeof(float);
+        HIPC(c, hipMalloc((void**)&c->d_grid, gh.bytes + box_bytes));
         HIPC(c, hipMemcpyAsync(c->d_grid, gh.image.data(), gh.bytes, hipMemcpyHostToDevice, c->stream));
+        HIPC(c, hipMemcpyAsync(c->d_grid + gh.bytes, gh.boxes.data(), box_bytes, hipMemcpyHostToDevice, c->stream));
         dg = dev_grid(gh, c->d_grid);
         c->grid_slow = gh.n_slow > 0;
         c->grid_wide = gh.wide;

@@ -16,7 +16,7 @@ namespace mm {
 // exit.  Not a product build: the counting perturbs the timing.
 enum LanePhase : int {
     kLpChunk, kLpBounce, kLpGlobal, kLpGridIter, kLpRectTest, kLpCellStep, kLpCert, kLpFallback,
-    kLpShade, kLpDiffuse, kLpTrial, kLpMirror, kLpCount
+    kLpShade, kLpDiffuse, kLpTrial, kLpMirror, kLpCertFull, kLpCount
 };
 
 // Closest-hit query methods of the wave-persistent kernel (MM_OPT_TRAVERSAL):
@@ -51,7 +51,8 @@ constexpr bool lds_static_grid(int mode) { return mode == kLdsGridImage || mode 
 constexpr bool lds_whole_search(int mode) { return mode == kLdsGridImage || mode == kLdsNodesRecs; }
 
 // Bytes a placement stages: BVH nodes are 2 x float4, compact slot records 5 x uint2; the grid image's
-// sections are [index: cells + lists | data at off_data: class table, records | boxes at off_box].
+// sections are [index: cells + lists | data at off_data: class table, records | windows at off_box]
+// ("boxes" below: the 24 B per rect at off_box, the fast certificate's windows; the leaf boxes are never staged).
 constexpr size_t lds_stage_bytes(int mode, uint32_t n_nodes, uint32_t n_rects, uint32_t grid_bytes,
                                  uint32_t grid_off_data, uint32_t grid_off_box) {
     switch (mode) {

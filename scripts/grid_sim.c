@@ -44,6 +44,7 @@ static void load(const char* path) {
 
 /* ---------------------------------------------------------------- grid */
 static float gmin[3], gcell[3], ginv[3], geps;
+static double gC;  /* the largest |coordinate| (>= 1): eps = 2^-14 C, the fast certificate's m = 2^-20 C */
 static int gn[3];
 static uint32_t* cell_off;   /* n_cells + 1 */
 static uint32_t* cell_list;
@@ -76,6 +77,7 @@ static void build_grid(double cell_target) {
         }
     }
     geps = (float)(C * 0x1p-14);
+    gC = C;
     if (cell_target <= 0) {  /* median of the rects' smaller nonzero extent */
         float* ext = malloc(4 * S.n_rects);
         uint32_t m = 0;
@@ -245,6 +247,7 @@ static inline float rect_a(v3 ori, v3 dir, const mm_rect* r) {
 
 typedef struct {
     uint64_t tail_q, tail_tests, tail_cells, big_face, dup_prev, dup_tests, queries, cells, tests, fallback_tie, fallback_verify, fallback_guard, mismatch, miss;
+    uint64_t cert_q, fast_ok, fast_bad;  /* CERTFAST: queries at the certificate, fast-accepted, of them failing the full one */
     uint64_t hist_cells[64];
 } gstats;
 
@@ -269,7 +272,38 @@ static float cell_time(int a, int b, float o, float y) {
     return fmaf((float)b, B, A);
 }
 
+/* CERTFAST=1: the fast certificate of mm_grid.h before the full one -- the hit point fma(best, d, o) inside the
+   inner window of R* (grid_build.cpp: its leaf's box shrunk by m = 2^-20 C on the in-plane axes, everything on the
+   normal axis k provided mn_k <= r_k <= mx_k) from an origin with |o| <= 8 C.  The full certificate is evaluated
+   as well: a fast-accepted query it fails is a violation. */
+static int certfast_on;
+static __thread int q_cert;  /* the last query: -1 no certificate ran, 1 fast-accepted, 0 took the full certificate */
+static int fast_cert(const float oo[3], const float dd[3], float best, uint32_t bk, const mm_node* L) {
+    const mm_rect* r = &S.rects[bk];
+    int ak = -1;
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, c = (a + 2) % 3;  /* axis-aligned, normal along a */
+        if (r->v[a] == 0.0f && r->u[a] == 0.0f && ((r->v[b] == 0.0f && r->u[c] == 0.0f) || (r->v[c] == 0.0f && r->u[b] == 0.0f)))
+            ak = a;
+    }
+    if (ak < 0 || !(L->mn[ak] <= r->o[ak] && r->o[ak] <= L->mx[ak])) return 0;
+    const float m = (float)ldexp(gC, -20), omax = (float)(8.0 * gC);
+    if (!(fmaxf(fmaxf(fabsf(oo[0]), fabsf(oo[1])), fabsf(oo[2])) <= omax)) return 0;
+    for (int a = 0; a < 3; ++a) {
+        if (a == ak) continue;
+        const double xl = (double)L->mn[a] + (double)m, xh = (double)L->mx[a] - (double)m;
+        const float c = (float)(0.5 * (xl + xh));
+        const double hd = fmin((double)c - xl, xh - (double)c) * (1.0 - 0x1p-22);
+        float h = (float)hd;
+        if ((double)h > hd) h = nextafterf(h, -INFINITY);
+        const float p = fmaf(best, dd[a], oo[a]);
+        if (!(fabsf(p - c) <= h)) return 0;
+    }
+    return 1;
+}
+
 static int grid_query(v3 o, v3 d, float* t_out, uint32_t* i_out, gstats* st) {
+    q_cert = -1;
     float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, yy[3];
     for (int a = 0; a < 3; ++a) {
         float ad = fabsf(dd[a]);
@@ -354,6 +388,12 @@ static int grid_query(v3 o, v3 d, float* t_out, uint32_t* i_out, gstats* st) {
     float tz1 = (L->mn[2] - o.z) / d.z, tz2 = (L->mx[2] - o.z) / d.z;
     tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
     (void)b;
+    if (certfast_on) {
+        q_cert = fast_cert(oo, dd, best, bk, L);
+        st->cert_q++;
+        st->fast_ok += q_cert;
+        if (q_cert && !(tmax >= tmin && tmax > 0.0f && tmin <= best)) st->fast_bad++;
+    }
     if (!(tmax >= tmin && tmax > 0.0f && tmin <= best)) { st->fallback_verify++; return 0; }
     *t_out = best;
     *i_out = bk;
@@ -363,6 +403,7 @@ static int grid_query(v3 o, v3 d, float* t_out, uint32_t* i_out, gstats* st) {
 /* wave model: per lane, per bounce, the list lengths of the visited cells */
 #define MAXB 32
 static __thread int w_len[64][MAXB][16], w_lx[64][MAXB][16], w_n[64][MAXB], w_nb[64], w_lane;
+static __thread signed char w_cert[64][MAXB];  /* q_cert per lane and bounce */
 /* DUMP=<file>: one 16-byte record per query, in path order, for the regrouping
    model (scripts/regroup_model.cpp): path id, bounce, start cell, octant, cells
    visited, the list length of the first 8 cells, and the rejection-sampling
@@ -408,6 +449,7 @@ static v3 path(v3 ori, v3 dir, uint32_t seed, int bl, int ml, gstats* st, trav_t
             w_n[w_lane][n] = q_n < 16 ? q_n : 16;
             for (int c = 0; c < w_n[w_lane][n]; ++c) { w_len[w_lane][n][c] = q_len[c]; w_lx[w_lane][n][c] = q_lx[c]; }
             w_nb[w_lane] = n + 1;
+            w_cert[w_lane][n] = (signed char)q_cert;
         }
         if (ok_q) {
             if (gt != b.t || (gt < BIG && gi != b.index)) {
@@ -484,7 +526,8 @@ int main(int argc, char** argv) {
     double wnest = 0, wflat = 0, wlane = 0, wcont[4] = {0, 0, 0, 0}, wtest = 0, wstep = 0, wshade = 0;
     double gnbmax = 0, gnbsum = 0, gnbw = 0, gact[32] = {0}, git[32] = {0};
     double gqmix = 0, gqsplit = 0, gitmix = 0, gitsplit = 0;
-    uint64_t rays_tot = 0;
+    uint64_t rays_tot = 0, waves_cert = 0, waves_slow = 0;
+    certfast_on = getenv("CERTFAST") != NULL;
 #pragma omp parallel
     {
         gstats st;
@@ -494,6 +537,7 @@ int main(int argc, char** argv) {
         double nest = 0, flat = 0, lanework = 0, ideal = 0, lockS = 0, cont[4] = {0, 0, 0, 0}, ntest = 0, nstep = 0;
         double nbmax = 0, nbsum = 0, nbw = 0, act_hist[32] = {0}, it_hist[32] = {0};
         double qmix = 0, qsplit = 0, itmix = 0, itsplit = 0;
+        uint64_t wv_cert = 0, wv_slow = 0;
 #pragma omp for schedule(dynamic, 1)
         for (int y = 0; y < H; y += rs)
             for (int x0 = 0; x0 < W; x0 += 64 / spp) {
@@ -524,6 +568,9 @@ int main(int argc, char** argv) {
                         if (fl > maxflat) maxflat = fl;
                     }
                     if (!any) break;
+                    { int cert = 0, slow = 0;  /* the wave of this chunk's queries at bounce b */
+                      for (int l = 0; l < 64; ++l) if (w_nb[l] > b) { cert |= w_cert[l][b] >= 0; slow |= w_cert[l][b] == 0; }
+                      wv_cert += cert; wv_slow += slow; }
                     for (int c = 0; c < maxc; ++c) {
                         int mx = 0, mxx = 0, mxz = 0;
                         for (int l = 0; l < 64; ++l) if (w_nb[l] > b && w_n[l][b] > c) {
@@ -582,6 +629,8 @@ int main(int argc, char** argv) {
             tot.fallback_guard += st.fallback_guard; tot.mismatch += st.mismatch; tot.miss += st.miss;
             for (int i = 0; i < 64; ++i) tot.hist_cells[i] += st.hist_cells[i];
             rays_tot += rays;
+            tot.cert_q += st.cert_q; tot.fast_ok += st.fast_ok; tot.fast_bad += st.fast_bad;
+            waves_cert += wv_cert; waves_slow += wv_slow;
         }
     }
     double q = (double)tot.queries;
@@ -606,5 +655,11 @@ int main(int argc, char** argv) {
     printf("cells hist:");
     for (int i = 1; i < 40; ++i) printf(" %d:%.3f", i, tot.hist_cells[i] / q);
     printf("\n");
-    return tot.mismatch ? 2 : 0;
+    if (certfast_on)
+        printf("fast certificate: %llu queries at the certificate, fast-accepted %llu (%.4f%%), of them failing the full "
+               "certificate %llu; 64-query waves with a certificate %llu, with a lane on the full certificate %llu (%.4f%%)\n",
+               (unsigned long long)tot.cert_q, (unsigned long long)tot.fast_ok, 100.0 * tot.fast_ok / (double)tot.cert_q,
+               (unsigned long long)tot.fast_bad, (unsigned long long)waves_cert, (unsigned long long)waves_slow,
+               100.0 * waves_slow / (double)waves_cert);
+    return tot.mismatch || tot.fast_bad ? 2 : 0;
 }
