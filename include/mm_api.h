@@ -258,6 +258,81 @@ int  mm_denoise_frames(mm_ctx* ctx, const float* color_dev, const mm_aov* guides
                        const mm_denoise_params* p, uint32_t n_frames,
                        uint32_t w, uint32_t h, void* out_dev);
 
+/* ---- temporal accumulation through mirror chains -----------------------------
+ * Carries a history through the frames of a camera sequence: every surface of
+ * the scene is matte or a perfect planar mirror, so the radiance a pixel shows
+ * does not depend on the camera as long as it shows the same surface point
+ * through the same mirrors.  normal_depth.w is the distance along the mirror
+ * chain, so cam.center + dist * primary_dir(p) is the virtual image of pixel
+ * p's surface point, the same world point for the camera of the frame before;
+ * projecting it there names the pixels that showed the point, with no motion
+ * vectors, and (id, mirror hits, normal, distance) confirm or refute each.
+ * Where the history holds, the output is the running mean of up to n_max
+ * frames; elsewhere it is the frame itself.  The output feeds
+ * mm_denoise_frames unchanged (which passes alpha through).
+ *
+ * uni: view_w and view_h (uni->cam is ignored).  cams: a HOST array of the
+ * n_frames cameras the frames and guides were traced with, copied into the
+ * launches' arguments: consumed on return.  color_dev, guides: n_frames*w*h
+ * elements, frame-major, what mm_trace_tile_cameras and mm_trace_aov write for
+ * the window (x0, y0, w, h) with y_stride 1 (neighbours must be frame
+ * neighbours; a multi-GPU caller accumulates the gathered frame).  out_dev:
+ * n_frames*w*h float4; out.a is the history length N, a float >= 1.  The last
+ * frame's output, guides and camera are what a later call takes as prev.
+ *
+ * All arithmetic is IEEE binary32, no contraction, in the order written; sqrtf
+ * and / are correctly rounded.  Frame f's history frame is frame f-1's OUTPUT
+ * of this call; for f = 0 it is prev, or none if prev is NULL.  Primed names
+ * are the history frame's (H' its colour).  rot(q, qw, v), the rotation
+ * primary_dir (shaders.metal:283) applies to its normalised direction:
+ *   nq = -q;  s1 = -((nq.x*v.x + nq.y*v.y) + nq.z*v.z)
+ *   c1 = (nq.y*v.z - nq.z*v.y, nq.z*v.x - nq.x*v.z, nq.x*v.y - nq.y*v.x)
+ *   v1 = c1 + qw*v
+ *   c2 = (v1.y*q.z - v1.z*q.y, v1.z*q.x - v1.x*q.z, v1.x*q.y - v1.y*q.x)
+ *   rot = (qw*v1 + s1*q) + c2                       (per component)
+ * For pixel p = (i, j) of frame f, px = x0 + i, py = y0 + j:
+ *   C = color[f][p]
+ *   NOHIST: out = (C.r, C.g, C.b, 1.0f)
+ *   if there is no history frame, or id_p is MM_AOV_ID_MISS or MM_AOV_ID_FAILED: NOHIST
+ *   d  = primary_dir(view, cams[f], px, py)       (the direction mm_trace_aov starts pixel p with)
+ *   X  = cam.center + nd_p.w * d                  (per component: one multiply, one add)
+ *   r  = X - cam'.center
+ *   l  = rot((-quat'.x, -quat'.y, -quat'.z), quat'.w, r)
+ *   dp = sqrtf((r.x*r.x + r.y*r.y) + r.z*r.z)
+ *   unless l.z > 0: NOHIST
+ *   sx = ((((l.x * cam'.focal) / l.z) + cam'.viewport[0]*0.5f) * view_w) / cam'.viewport[0]
+ *   sy = ((((l.y * cam'.focal) / l.z) + cam'.viewport[1]*0.5f) * view_h) / cam'.viewport[1]
+ *   u = sx - (float)x0;  v = sy - (float)y0
+ *   unless u >= -1.0f && u < (float)w && v >= -1.0f && v < (float)h: NOHIST     (a NaN fails)
+ *   fu = floorf(u); a = u - fu; i0 = (int)fu;   fv = floorf(v); b = v - fv; j0 = (int)fv
+ *   S = (0,0,0); SN = 0; W = 0
+ *   for (dx,dy) in (0,0), (1,0), (0,1), (1,1):
+ *     q = (i0+dx, j0+dy); skip q outside [0,w) x [0,h)
+ *     skip unless id'_q == id_p (all 32 bits)  and  al'_q.w == al_p.w
+ *            and (nd_p.x*nd'_q.x + nd_p.y*nd'_q.y) + nd_p.z*nd'_q.z >= 0
+ *            and fabsf(dp - nd'_q.w) <= tol_z * (dp + nd'_q.w)
+ *     g = (dx ? a : 1.0f - a) * (dy ? b : 1.0f - b)
+ *     S.c = S.c + g * H'_q.c  (c = r, g, b);  SN = SN + g * H'_q.a;  W = W + g
+ *   unless W >= w_min: NOHIST
+ *   Hc = S / W;  N = fminf(SN / W + 1.0f, (float)n_max)
+ *   out.rgb = Hc + (C.rgb - Hc) / N;  out.a = N
+ *
+ * MM_ERR_INVALID: a null argument other than prev, a null pointer in guides or
+ * in prev (its colour, its guides); n_max outside 1..65535, tol_z not > 0 or
+ * not finite, w_min outside (0, 1] (a NaN is outside), flags not 0; w, h or
+ * n_frames 0; a misaligned pointer (float4: 16 bytes, id: 4); out_dev
+ * overlapping color_dev, a guide or a prev buffer (prev may be an earlier
+ * call's out_dev, not this one's); w*h over 2^31 - 1, x0 + w or y0 + h over
+ * 2^24 (the float conversions are then exact), or more than 2^40 pixels in
+ * all.  Enqueued on the context's stream like mm_denoise_frames, one launch per
+ * frame in stream order; the inputs are never written.  The call keeps no
+ * scratch (frame f reads frame f-1 from out_dev) and needs no uploaded scene. */
+int  mm_accumulate_frames(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams,
+                          const float* color_dev, const mm_aov* guides,
+                          const mm_temporal_prev* prev, const mm_temporal_params* p,
+                          uint32_t n_frames, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                          void* out_dev);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

@@ -109,6 +109,21 @@ typedef struct mm_denoise_params {   /* 16 bytes */
     uint32_t flags;     /* MM_DN_RGBA8 */
 } mm_denoise_params;
 
+/* Parameters of mm_accumulate_frames (mm_api.h): temporal accumulation of a
+ * camera sequence's frames, the history reprojected through the mirror chains. */
+typedef struct mm_temporal_params {   /* 16 bytes */
+    uint32_t n_max;   /* 1..65535: history length cap (blend factor 1/min(N, n_max)) */
+    float    tol_z;   /* > 0: relative distance tolerance of a history tap */
+    float    w_min;   /* in (0, 1]: least sum of valid bilinear weights that counts as history */
+    uint32_t flags;   /* 0 */
+} mm_temporal_params;
+
+typedef struct mm_temporal_prev {     /* the frame before frame 0, from an earlier call */
+    const float* color;   /* DEVICE, w*h float4: an earlier call's out frame (alpha = N) */
+    mm_aov       guides;  /* DEVICE, that frame's three buffers (one frame), all required */
+    mm_camera    cam;     /* that frame's camera */
+} mm_temporal_prev;
+
 /* Return codes (0 = success; never panics or throws across the ABI). */
 #define MM_OK               0
 #define MM_ERR_INVALID     -1  /* bad argument / shape                        */

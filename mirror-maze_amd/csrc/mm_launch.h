@@ -145,6 +145,25 @@ struct DnPass {
 hipError_t launch_denoise_keys(const float4* al, const uint32_t* id, uint2* keys, size_t n, hipStream_t s);
 hipError_t launch_denoise_pass(const DnPass& pass, hipStream_t s);
 
+// One frame of mm_accumulate_frames (temporal_kernels.hip); every pointer points at one frame.
+struct TpFrame {
+    const float4* color = nullptr;   // the frame as traced
+    const float4* nd = nullptr;      // its guides
+    const float4* al = nullptr;
+    const uint32_t* id = nullptr;
+    const float4* h_color = nullptr; // the history frame's output (alpha = N); nullptr: no history frame
+    const float4* h_nd = nullptr;    // its guides
+    const float4* h_al = nullptr;
+    const uint32_t* h_id = nullptr;
+    float4* out = nullptr;
+    mm_camera cam{}, h_cam{};        // the frame's and the history frame's camera
+    float view_w = 0.0f, view_h = 0.0f;
+    uint32_t x0 = 0, y0 = 0, w = 0, h = 0;  // w * h < 2^31; x0 + w, y0 + h <= 2^24
+    uint32_t tiles_x = 0;                   // set by the launcher
+    float n_max = 1.0f, tol_z = 0.0f, w_min = 0.0f;      // n_max as a float (exact: at most 65535)
+};
+hipError_t launch_temporal_frame(const TpFrame& frame, hipStream_t s);
+
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);
 

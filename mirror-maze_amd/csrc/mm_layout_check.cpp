@@ -28,5 +28,11 @@ static_assert(sizeof(mm_aov) == 24 && offsetof(mm_aov, albedo) == 8 && offsetof(
 static_assert(sizeof(mm_denoise_params) == 16 && offsetof(mm_denoise_params, sigma_z) == 4 &&
                   offsetof(mm_denoise_params, flags) == 12,
               "mm_denoise_params is four 4-byte fields");
+static_assert(sizeof(mm_temporal_params) == 16 && offsetof(mm_temporal_params, tol_z) == 4 &&
+                  offsetof(mm_temporal_params, w_min) == 8 && offsetof(mm_temporal_params, flags) == 12,
+              "mm_temporal_params is four 4-byte fields");
+static_assert(sizeof(mm_temporal_prev) == 72 && offsetof(mm_temporal_prev, guides) == 8 &&
+                  offsetof(mm_temporal_prev, cam) == 32,
+              "mm_temporal_prev is a pointer, an mm_aov and an mm_camera");
 
 extern "C" int mm_layout_ok(void) { return 1; }

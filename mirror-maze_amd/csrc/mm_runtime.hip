@@ -751,6 +751,76 @@ int mm_denoise_frames(mm_ctx* c, const float* color_dev, const mm_aov* guides, c
     return MM_OK;
 }
 
+int mm_accumulate_frames(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const float* color_dev,
+                         const mm_aov* guides, const mm_temporal_prev* prev, const mm_temporal_params* p,
+                         uint32_t n_frames, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out_dev) {
+    // (argument checks first, and none of them needs the context, as in mm_denoise_frames)
+    if (!u || !cams || !color_dev || !guides || !p || !out_dev)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: null argument");
+    if (!guides->normal_depth || !guides->albedo || !guides->id)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: all three guide buffers are required");
+    if (prev && (!prev->color || !prev->guides.normal_depth || !prev->guides.albedo || !prev->guides.id))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: prev needs its colour and all three guide buffers");
+    if (p->n_max < 1 || p->n_max > 65535) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: n_max must be 1..65535");
+    if (!(p->tol_z > 0.0f) || !std::isfinite(p->tol_z))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: tol_z must be positive and finite");
+    if (!(p->w_min > 0.0f && p->w_min <= 1.0f))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: w_min must be in (0, 1]");
+    if (p->flags) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: unknown flags");
+    if (w == 0 || h == 0 || n_frames == 0)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: empty tile or no frames");
+    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
+    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
+        misaligned(guides->id, 4) || misaligned(out_dev, 16) ||
+        (prev && (misaligned(prev->color, 16) || misaligned(prev->guides.normal_depth, 16) ||
+                  misaligned(prev->guides.albedo, 16) || misaligned(prev->guides.id, 4))))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: misaligned buffer (float4: 16 bytes, id: 4)");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: more pixels than one call holds");
+    if ((uint64_t)x0 + w > (1ull << 24) || (uint64_t)y0 + h > (1ull << 24))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: the window ends beyond pixel 2^24");
+    const uint64_t n_all = n_pix * n_frames, out_bytes = n_all * 16;
+    if (ranges_overlap(out_dev, out_bytes, color_dev, n_all * 16) ||
+        ranges_overlap(out_dev, out_bytes, guides->normal_depth, n_all * 16) ||
+        ranges_overlap(out_dev, out_bytes, guides->albedo, n_all * 16) ||
+        ranges_overlap(out_dev, out_bytes, guides->id, n_all * 4) ||
+        (prev && (ranges_overlap(out_dev, out_bytes, prev->color, n_pix * 16) ||
+                  ranges_overlap(out_dev, out_bytes, prev->guides.normal_depth, n_pix * 16) ||
+                  ranges_overlap(out_dev, out_bytes, prev->guides.albedo, n_pix * 16) ||
+                  ranges_overlap(out_dev, out_bytes, prev->guides.id, n_pix * 4))))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: the output overlaps an input");
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    // One launch per frame, in stream order: frame f reads frame f - 1's output, which the kernel boundary makes
+    // visible.  The cameras travel in the launches' arguments, so `cams` is consumed when this returns and the
+    // call keeps no scratch.
+    TpFrame a;
+    a.view_w = u->view_w; a.view_h = u->view_h;
+    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
+    a.n_max = (float)p->n_max; a.tol_z = p->tol_z; a.w_min = p->w_min;
+    if (prev) {
+        a.h_color = reinterpret_cast<const float4*>(prev->color);
+        a.h_nd = reinterpret_cast<const float4*>(prev->guides.normal_depth);
+        a.h_al = reinterpret_cast<const float4*>(prev->guides.albedo);
+        a.h_id = prev->guides.id;
+        a.h_cam = prev->cam;
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const size_t o = (size_t)f * n_pix;
+        a.color = reinterpret_cast<const float4*>(color_dev) + o;
+        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
+        a.al = reinterpret_cast<const float4*>(guides->albedo) + o;
+        a.id = guides->id + o;
+        a.out = reinterpret_cast<float4*>(out_dev) + o;
+        a.cam = cams[f];
+        HIPC(c, launch_temporal_frame(a, c->stream));
+        a.h_color = a.out; a.h_nd = a.nd; a.h_al = a.al; a.h_id = a.id;
+        a.h_cam = a.cam;
+    }
+    return MM_OK;
+}
+
 int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
     if (!c) return MM_ERR_INVALID;
     if (!c->d_fb) return fail(c, MM_ERR_INVALID, "mm_read_framebuffer: nothing rendered yet");

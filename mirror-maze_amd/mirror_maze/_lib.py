@@ -89,6 +89,14 @@ class mm_denoise_params(C.Structure):
     _fields_ = [("n_passes", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("flags", C.c_uint32)]
 
 
+class mm_temporal_params(C.Structure):
+    _fields_ = [("n_max", C.c_uint32), ("tol_z", C.c_float), ("w_min", C.c_float), ("flags", C.c_uint32)]
+
+
+class mm_temporal_prev(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("guides", mm_aov), ("cam", mm_camera)]
+
+
 class mm_rng(C.Structure):
     _fields_ = [("key", C.c_uint32 * 8), ("counter", C.c_uint64), ("buf", C.c_uint32 * 64), ("pos", C.c_uint32)]
 
@@ -132,6 +140,9 @@ EXPORTS = {
                                C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mm_aov)]),
     "mm_denoise_frames": (C.c_int, [P, P, C.POINTER(mm_aov), C.POINTER(mm_denoise_params), C.c_uint32, C.c_uint32,
                                     C.c_uint32, P]),
+    "mm_accumulate_frames": (C.c_int, [P, C.POINTER(mm_uniform), P, P, C.POINTER(mm_aov), C.POINTER(mm_temporal_prev),
+                                       C.POINTER(mm_temporal_params), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, P]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

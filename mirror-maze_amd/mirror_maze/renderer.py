@@ -348,6 +348,71 @@ class Renderer:
                                             out.data_ptr()))
         return out
 
+    def _aov_frames(self, aov, n, h, w, device, what):
+        """The mm_aov of an aov dict whose buffers hold n frames of h x w on `device`."""
+        import torch
+
+        if not (isinstance(aov, dict) and all(k in aov for k in self.AOV_NAMES)):
+            raise ValueError(f"{what} must hold the buffers {self.AOV_NAMES} of trace_aov")
+        for k in self.AOV_NAMES:
+            shape, dt = ((n, h, w), torch.int32) if k == "id" else ((n, h, w, 4), torch.float32)
+            t = aov[k]
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == device and t.dtype == dt and t.is_contiguous()
+                    and tuple(t.shape) in (shape, shape[1:] if n == 1 else shape)):
+                raise ValueError(f"{what}[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {device}")
+        return _lib.mm_aov(*[aov[k].data_ptr() for k in self.AOV_NAMES])
+
+    def accumulate(self, uniform: _lib.mm_uniform, cameras, color, aov, prev=None, n_max: int = 32,
+                   tol_z: float = 0.02, w_min: float = 0.25, x0: int = 0, y0: int = 0, out=None):
+        """Temporal accumulation of a camera sequence (mm_accumulate_frames).
+        `color`: the (h, w, 4) or (n, h, w, 4) float32 CUDA tensor
+        trace_tile_cameras returned for `cameras` over the window (x0, y0, w,
+        h) of uniform's view with y_stride 1; `aov`: what trace_aov returned
+        for the same window and cameras (all three buffers).  Every pixel's
+        surface point -- its virtual image, when it is seen through mirrors --
+        is projected into the frame before; where the pixels there show the
+        same point through the same mirrors (id, mirror hits, normal, distance
+        within tol_z; valid bilinear weight at least w_min) the output is the
+        running mean of up to n_max frames, elsewhere the frame itself.  The
+        frame before frame 0 is `prev`, a (color, aov, camera) triple: an
+        earlier call's last output frame, that frame's guides and its camera;
+        None starts a new history.  Returns a float32 tensor of color's shape
+        (`out` if given) whose alpha is the history length; it feeds denoise()
+        unchanged.  The inputs are not written."""
+        import torch
+
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+                and color.dim() in (3, 4) and color.shape[-1] == 4):
+            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
+        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        cams = self._cameras(cameras)
+        if cams.shape[0] != n:
+            raise ValueError(f"{n} frames need {n} cameras, not {cams.shape[0]}")
+        a = self._aov_frames(aov, n, h, w, color.device, "aov")
+        if not 1 <= int(n_max) <= 65535:
+            raise ValueError("n_max must be 1..65535")
+        if out is None:
+            out = torch.empty_like(color)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
+                  and out.dtype == torch.float32 and out.shape == color.shape):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of color's shape")
+        pv = None
+        if prev is not None:
+            pc, pa, pcam = prev
+            if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == color.device and pc.dtype == torch.float32
+                    and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
+                raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {color.device}")
+            pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
+            pv = _lib.mm_temporal_prev(pc.data_ptr(), self._aov_frames(pa, 1, h, w, color.device, "prev's aov"),
+                                       _lib.mm_camera.from_buffer_copy(pcam.tobytes()))
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
+        self._check(lib().mm_accumulate_frames(self._ctx, C.byref(uniform), cams.ctypes.data, color.data_ptr(),
+                                               C.byref(a), None if pv is None else C.byref(pv), C.byref(p), n, x0, y0,
+                                               w, h, out.data_ptr()))
+        return out
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the

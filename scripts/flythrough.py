@@ -11,6 +11,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 10 --frames 30 --no-render     # the camera path only: no GPU
     python scripts/flythrough.py --maze 32 --frames 40 --aov aov/       # + feature buffers per frame
     python scripts/flythrough.py --maze 32 --frames 40 --denoise        # + frame_NNNN_dn.png beside each frame
+    python scripts/flythrough.py --maze 32 --frames 40 --accumulate     # + frame_NNNN_acc.png beside each frame
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
@@ -23,6 +24,12 @@ Renderer.denoise (mm_denoise_frames, its default passes and sigmas), guided by
 the batch's feature buffers -- traced for it if --aov did not ask for them.  The
 batch is then traced as float frames; frame_NNNN.png is their RGBA8 conversion,
 the same bytes as without --denoise.
+
+--accumulate also writes frame_NNNN_acc.png beside each frame: the frame through
+Renderer.accumulate (mm_accumulate_frames, its defaults), the running mean of
+the frames before it wherever they showed the same surface point through the
+same mirrors; the history carries over from batch to batch.  With --denoise the
+denoiser then runs on the accumulated frames (frame_NNNN_dn.png).
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -65,6 +72,9 @@ def main(argv=None) -> int:
                     help="also write per-frame feature buffers: DIR/frame_NNNN/{normal.png,depth.npy,id.npy}")
     ap.add_argument("--denoise", action="store_true",
                     help="also write frame_NNNN_dn.png: the frame through Renderer.denoise, guided by its feature buffers")
+    ap.add_argument("--accumulate", action="store_true",
+                    help="also write frame_NNNN_acc.png: the frame through Renderer.accumulate (temporal accumulation); "
+                         "with --denoise the denoiser runs on the accumulated frames")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
@@ -90,21 +100,31 @@ def main(argv=None) -> int:
     out_dir = Path(a.out)
     out_dir.mkdir(parents=True, exist_ok=True)
     u = player.uniform()  # view size and chunk width; its camera is not used
+    floats = a.denoise or a.accumulate  # the batch is traced as float frames
+    prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera
     with Renderer(0) as r:
         r.upload_scene(scene)
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
-            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not a.denoise)
-            frames = (r.quantize(img) if a.denoise else img).cpu().numpy()
+            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not floats)
+            frames = (r.quantize(img) if floats else img).cpu().numpy()
             r.sync()
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
             print(f"# frames {f0}..{f0 + len(batch) - 1}: one launch, {out_dir}/frame_{f0:04d}.png ...", flush=True)
-            if a.aov is None and not a.denoise:
+            if a.aov is None and not floats:
                 continue
             bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
-                               want=Renderer.AOV_NAMES if a.denoise else ("normal_depth", "id"))
+                               want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
+            if a.accumulate:
+                img = r.accumulate(u, batch, img, bufs, prev=prev)
+                prev = (img[-1], {k: v[-1:] for k, v in bufs.items()}, batch[-1])
+                acc = r.quantize(img).cpu().numpy()
+                r.sync()
+                for k in range(len(batch)):
+                    write_png(out_dir / f"frame_{f0 + k:04d}_acc.png", acc[k])
+                print(f"# frames {f0}..{f0 + len(batch) - 1}: accumulated, {out_dir}/frame_{f0:04d}_acc.png ...", flush=True)
             if a.denoise:
                 clean = r.denoise(img, bufs, rgba8=True).cpu().numpy()
                 r.sync()
