@@ -402,6 +402,10 @@ int  mm_set_pipeline(mm_ctx* ctx, int pipe);
 #define MM_OPT_GRID_WIDE  26  /* grid search: 1 (default) 64-bit cell words with per-face list ranges where the
                                   image fits the LDS budget; 0 plain 32-bit words (whole list per cell).  Read
                                   by mm_upload_scene */
+#define MM_OPT_PREDRAW    27  /* wave-persistent kernel: rejection-sampling trials a chunk of new paths draws
+                                  per path before its bounces, acceptance only, into the path's trial window
+                                  (0..31; -1 default: 3 * bounce_limit, at most 31 -- 24 at 8 bounces,
+                                  scripts/predraw_model.py, profiles/predraw/).  Results never depend on it */
 #define MM_OPT_FAULT_INJECT 23 /* tests of the error path (results are then invalid): 0 off (default); 1 every
                                   wave-persistent launch raises an injected fault (error bit 3); 2 the tail
                                   rings' protocol waits give up at once (bit 2 when a wait was needed; a

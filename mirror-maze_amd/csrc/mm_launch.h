@@ -25,8 +25,8 @@ using Sample = F3;
 static_assert(sizeof(Sample) == 12, "three floats, no padding");
 
 // Deferred path states (mirror-tail deferral): one 64-byte record per entry
-// (rec[4*i .. 4*i+3] = ori.xyz dir.x | dir.yz T.xy | T.z L.xyz | seed,
-// (n - mh) | mh << 15 | bank << 30, sample slot, s1 -- one base pointer; 16 SoA field arrays would
+// (rec[4*i .. 4*i+3] = ori.xyz dir.x | dir.yz T.xy | T.z L.xyz | sb,
+// (n - mh) | mh << 15, sample slot, mask: the trial window -- one base pointer; 16 SoA field arrays would
 // hold 15 addresses in SGPRs across the bounce loop), `cap` records; resident
 // block b owns the kTailRing records from b * kTailRing (its tail ring, at most
 // 2 blocks per CU; kTailRing: mm_variants.h).
@@ -87,6 +87,10 @@ struct TileJob {
     // deferred path is lost (bit 4, and the reader's ring timeout) -- tests of
     // the error path.
     uint32_t fault = 0;
+    // Trials of the rejection sampling a new-path chunk draws into each path's
+    // window before its bounces (MM_OPT_PREDRAW, mm_plan.cpp; 0..31; mm_trace.h
+    // predraw_trials).  Results never depend on it.
+    uint32_t predraw = 0;
     // Camera sequence (mm_trace_tile_cameras): frame f of the launch is traced with camera record f of this
     // device array (kCamStride floats per record: an mm_camera, padded to 64 B) instead of u.cam.  Null:
     // u.cam for every frame.  (Last member: the offsets of the fields above are those of the launches

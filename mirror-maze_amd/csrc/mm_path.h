@@ -104,7 +104,7 @@ __device__ __forceinline__ bool bounce_loop_r(const DevScene& sc, const Q& query
         // a failed query (the BVH stack overflowed) ends the path as a miss
         // does -- L kept -- so that no exit bypasses the shading step
         overflow |= !ok;
-        const bool more = shade_step(sc, p, ok ? t : kBig, k, mirror_limit);
+        const bool more = shade_step(sc, p, ok ? t : kBig, k, bounce_limit, mirror_limit);
 #ifdef MM_PHASE_CLOCKS
         c.s_cyc += (uint64_t)wall_clock64() - t1;
 #endif
@@ -130,13 +130,12 @@ __device__ __forceinline__ F3 trace_path(const DevScene& sc, const Q& query, F3 
                                          int bounce_limit, int mirror_limit, ScratchStack& stack, Counters& c,
                                          bool& overflow) {
     PathState p;
-    p.ori = ori; p.dir = dir; p.seed = seed;
+    p.ori = ori; p.dir = dir; p.sb = seed;
     p.T = F3{1.0f, 1.0f, 1.0f};
     p.L = F3{0.0f, 0.0f, 0.0f};
     p.n = 0;
     p.mh = 0;
-    p.bank = 0u;
-    p.s1 = 0u;
+    p.mask = 1u;  // an empty trial window (no pre-pass: the parity and reference kernels)
     bounce_loop<kStats>(sc, query, p, bounce_limit, mirror_limit, stack, c, overflow);
     return F3{sqrtf(fmaxf(p.L.x, 0.0f)), sqrtf(fmaxf(p.L.y, 0.0f)), sqrtf(fmaxf(p.L.z, 0.0f))};
 }

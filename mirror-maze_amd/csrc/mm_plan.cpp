@@ -81,6 +81,17 @@ Choice choose_placement(const SceneFacts& f, const PlanOptions& o, int form) {
     return c;
 }
 
+// A path of bounce_limit b reads b - 1 direction samples when it meets no mirror (its last bounce reads
+// none), 1.91 trials each at acceptance pi / 6, and a wave runs a round in the bounce whenever one of its 64
+// lanes has run out.  The wave model (scripts/predraw_model.py, profiles/predraw/model.txt) puts the cheapest
+// pre-pass at bounce_limit 8 near 22 trials with a flat minimum, and C3 measured fastest at 24 (1.865 ms/frame;
+// 20: 1.881, 28: 1.897, 16: 1.932, 31: 1.931, 0: 2.058 -- profiles/predraw/ab_k_sweep.txt): 3 b, capped by
+// the window's 31.
+uint32_t plan_predraw(int opt_predraw, uint32_t bounce_limit) {
+    if (opt_predraw >= 0) return std::min<uint32_t>((uint32_t)opt_predraw, 31u);
+    return (uint32_t)std::min<uint64_t>(3ull * bounce_limit, 31u);
+}
+
 LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mode, const size_t static_lds[2],
                      const mm_ext& e, uint32_t w, uint32_t h, uint32_t n_frames, const char* multi_fn) {
     const bool multi = multi_fn != nullptr;
@@ -108,6 +119,7 @@ LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mo
                                   "method / LDS placement (grid search, or BVH form 7 with nodes + "
                                   "records in LDS)");
     LaunchPlan p;
+    p.predraw = plan_predraw(o.opt_predraw, e.bounce_limit);
     p.defer = defer_built && (defer_on || wave) && (wave || tile_paths * n_frames >= o.opt_defer_min);
     // the deferral kernel's static LDS (tail ring, claimed queue ranges, and with ring kind 2 the rings'
     // 32 KB of records) must leave two 1024-thread blocks per CU: the records go to LDS where the

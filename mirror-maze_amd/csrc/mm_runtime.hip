@@ -85,6 +85,7 @@ PlanOptions plan_options(const mm_ctx* c) {
     o.pipe = c->pipe; o.opt_ww = c->opt_ww; o.opt_lds = c->opt_lds; o.opt_lds_rects = c->opt_lds_rects;
     o.opt_fuse = c->opt_fuse; o.opt_persist = c->opt_persist; o.opt_defer = c->opt_defer;
     o.opt_defer_min = c->opt_defer_min;
+    o.opt_predraw = c->opt_predraw;
     return o;
 }
 
@@ -444,6 +445,10 @@ int mm_set_option(mm_ctx* c, int key, int value) {
         case MM_OPT_GRID_CELL:
             if (value < 25 || value > 400) return fail(c, MM_ERR_INVALID, "grid cell scale must be 25..400 (%)");
             c->opt_grid_cell = value;
+            return MM_OK;
+        case MM_OPT_PREDRAW:
+            if (value < -1 || value > 31) return fail(c, MM_ERR_INVALID, "pre-drawn trials must be -1 (auto) or 0..31");
+            c->opt_predraw = value;
             return MM_OK;
         case MM_OPT_FAULT_INJECT:
             if (value < 0 || value > 4) return fail(c, MM_ERR_INVALID, "fault inject must be 0..4");
@@ -919,6 +924,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
         job.n_frames = n_frames;
         job.cams = cams_dev;
         job.reserve_cus = c->opt_reserve_cus;
+        job.predraw = plan.predraw;
         job.fault = (c->opt_fault == 1 || c->opt_fault == 4) ? (uint32_t)c->opt_fault : 0u;
         if (c->opt_fault == 2) job.ring_spin = 0;
         if (defer) {

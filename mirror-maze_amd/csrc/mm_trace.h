@@ -462,17 +462,18 @@ __device__ __forceinline__ bool closest_hit_bvh(const DevScene& sc, const V& v, 
     }
 }
 
-// Path state carried across bounces.  bank (0..2): accepted rejection-sampling
-// trials already drawn from the RNG for the path's next diffuse bounces
-// (shade_step): with bank >= 1 the first ends at s1 (its three numbers are the
-// three draws before state s1), with bank = 2 the second ends at `seed`; with
-// bank = 1 `seed` may lie past s1 by rejected trials only.
+// Path state carried across bounces.  (sb, mask) is the path's trial window
+// on its RNG stream: sb is the stream state at the first trial that no bounce
+// has consumed yet, bit i of mask tells that trial i from there was accepted
+// by the rejection sampling (shade_step), and the highest set bit is a
+// sentinel above the trials drawn so far -- mask = 1: none drawn; room for 31.
 struct PathState {
     F3 ori, dir, T, L;
-    uint32_t seed;
+    uint32_t sb;
     int n, mh;
-    uint32_t bank, s1;
+    uint32_t mask;
 };
+constexpr uint32_t kTrialWindow = 31;
 
 // random()'s state step s -> a s + c (shaders.metal:181-186, rand_pm1), and the
 // inverse of three steps: s0 = A s3 + C with A = a^-3, C = -A c (1 + a + a^2)
@@ -489,6 +490,69 @@ static_assert(kLcgA * kLcgA * kLcgA * kLcgBack3A == 1u, "a^3 * a^-3 = 1 mod 2^32
 static_assert(kLcgBack3A * (((kLcgA * 12345u + kLcgC) * kLcgA + kLcgC) * kLcgA + kLcgC) + kLcgBack3C == 12345u,
               "three steps rewound");
 
+// Jumps over whole trials: entry i = (A3, C3) with A3 s + C3 the state 3 i
+// steps (i trials) after s, i = 0..31 -- the start of trial i of a window
+// whose base is s.  Entry 31 skips a full window of rejected trials.
+struct LcgJump3 {
+    uint32_t ac[2 * (kTrialWindow + 1)];
+};
+constexpr LcgJump3 lcg_jump3() {
+    LcgJump3 j{};
+    uint32_t a = 1u, c = 0u;
+    for (uint32_t i = 0; i <= kTrialWindow; ++i) {
+        j.ac[2 * i] = a;
+        j.ac[2 * i + 1] = c;
+        for (int k = 0; k < 3; ++k) {  // one more step after the jump: a' s + c' = kLcgA (a s + c) + kLcgC
+            a = kLcgA * a;
+            c = kLcgA * c + kLcgC;
+        }
+    }
+    return j;
+}
+constexpr LcgJump3 kLcgJump3 = lcg_jump3();
+constexpr uint32_t lcg_steps(uint32_t s, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) s = s * kLcgA + kLcgC;
+    return s;
+}
+constexpr bool lcg_jump3_ok() {
+    for (uint32_t i = 0; i <= kTrialWindow; ++i)
+        if (kLcgJump3.ac[2 * i] * 12345u + kLcgJump3.ac[2 * i + 1] != lcg_steps(12345u, 3u * i)) return false;
+    return true;
+}
+static_assert(kLcgJump3.ac[0] == 1u && kLcgJump3.ac[1] == 0u, "entry 0 is the identity");
+static_assert(lcg_jump3_ok(), "entry i is 3 i single steps");
+static_assert(kLcgJump3.ac[2] * kLcgBack3A == 1u, "entry 1 inverts the three-step rewind");
+// the table in constant memory, one 8-byte (A3, C3) read per lane
+static __constant__ const LcgJump3 kLcgJump3Dev = lcg_jump3();
+__device__ __forceinline__ uint32_t lcg_jump_trials(uint32_t s, uint32_t i) {
+    const uint2 j = reinterpret_cast<const uint2*>(kLcgJump3Dev.ac)[i & kTrialWindow];  // (& 31: never out of the table)
+    return s * j.x + j.y;
+}
+
+// One rejection-sampling trial from state s (shaders.metal:315-318): its three
+// numbers and 1 if it is accepted.  Rejected iff length(r) > 1, and
+// RN(sqrt(x)) > 1 <=> x > 1 + 2^-23 for every binary32 x (exhaustive check:
+// scripts/verify_sqrt_gt1.c); accepted <=> !(q2 > 1 + 2^-23) <=> q2 < 1 + 2^-22
+// <=> the sign of the exact difference (q2 is finite) -- two pairable ops
+// instead of a compare and a select.
+__device__ __forceinline__ uint32_t trial_accepted(uint32_t& s) {
+    const float rx = rand_pm1(s), ry = rand_pm1(s), rz = rand_pm1(s);
+    const float q2 = dot3(F3{rx, ry, rz}, F3{rx, ry, rz});
+    return __float_as_uint(q2 - 0x1.000004p0f) >> 31;
+}
+
+// The pre-pass of a new-path chunk: the first k trials of the path's stream
+// (after the primary jitter) drawn into its window at full lane utilisation,
+// acceptance only.  k (0..31) is wave-uniform; results never depend on it.
+__device__ __forceinline__ void predraw_trials(PathState& p, uint32_t k) {
+    uint32_t s = p.sb, mask = 0u;
+    for (uint32_t r = 0; r < k; ++r) {
+        MM_LANE_STAT(kLpPredraw);
+        mask |= trial_accepted(s) << r;
+    }
+    p.mask = mask | (1u << k);
+}
+
 // One shading step after a closest-hit query (the body of shaders.metal:306-340
 // after line 307).  Returns false when the path terminates.
 // A terminating path (a miss, shaders.metal:336-338, or a mirror bounce past
@@ -498,7 +562,8 @@ static_assert(kLcgBack3A * (((kLcgA * 12345u + kLcgC) * kLcgA + kLcgC) * kLcgA +
 // unconditionally and the bounce loop carries one copy of it (with early
 // returns the old and the new state were live together and the compiler copied
 // the whole state between register sets twice per bounce).
-__device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, float t, uint32_t k, int mirror_limit) {
+__device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, float t, uint32_t k, int bounce_limit,
+                                           int mirror_limit) {
     const bool hit = t < kBig;
     k = hit ? k : 0u;
     MM_LANE_STAT(kLpShade);
@@ -518,55 +583,46 @@ __device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, flo
         const float4 e = sc.shade[2 * k + 1];
         contrib = (e.w * p.T) * xyz(e);                      // %253, %254
         p.T = xyz(s0) * p.T;                                 // %264
-        // shaders.metal:316-318, length(r) > 1: RN(sqrt(x)) > 1 <=> x > 1 + 2^-23
-        // for every binary32 x (exhaustive check: scripts/verify_sqrt_gt1.c).
-        // The path's direction samples are its RNG stream's accepted trials in
-        // order -- nothing else draws from it after the primary jitter -- so a
-        // lane may draw ahead, and may skip rejected trials it already drew.
-        // The first trial: the first banked one (its draws rewound from s1 and
-        // redrawn: the same numbers; the stream goes on from `seed`, past any
-        // rejected trials after it), else a fresh one.  Lanes whose trial is
-        // rejected loop; while they do, the wave's other diffuse lanes draw
-        // their NEXT bounces' trials until two are accepted (the bank), so those
-        // bounces' first trials are accepted on those lanes and the wave's loop
-        // runs for fewer lanes -- a wave runs its unluckiest lane's trials (~5.8
-        // iterations per bounce on C3 where a lane needs 0.9; a CPU model of 64
-        // lanes: 3.3 with a bank of one, 2.6 with two).  (A wave-pooled form --
-        // trials spread over the lanes with jumps of the state -- was bit-exact
-        // and slower: 12 % on C3 in round 2, 3.5 % in round 3,
-        // profiles/r03/ab_pool_trials.txt.)
-        uint32_t s = p.bank ? p.s1 : p.seed;
-        if (p.bank) s = s * kLcgBack3A + kLcgBack3C;
-        float rx = rand_pm1(s), ry = rand_pm1(s), rz = rand_pm1(s);
-        p.seed = p.bank ? p.seed : s;
-        p.s1 = p.seed;  // (the second banked trial, if any, ends there: it is the first now)
-        uint32_t bank = p.bank ? p.bank - 1u : 0u;
-        F3 rd = F3{rx, ry, rz};
-        float len2 = dot3(rd, rd);
-        uint32_t need = len2 > 0x1.000002p0f ? 1u : 0u;
-        if (__builtin_amdgcn_ballot_w64(need != 0u)) do {  // (do-while: no copies of the carried values)
+        // shaders.metal:316-318.  The path's direction samples are its RNG
+        // stream's accepted trials in order -- nothing else draws from it after
+        // the primary jitter -- so a lane may draw ahead, and may skip rejected
+        // trials it already drew.  Which trials were accepted is drawn ahead
+        // into the path's window (sb, mask): mostly by the pre-pass at the
+        // chunk's start (predraw_trials, every lane busy), and here, one round
+        // for every diffuse lane with room, only while a lane that will read
+        // its new direction has no accepted trial left -- a wave runs its
+        // unluckiest lane's rounds.  The lane then takes its first accepted
+        // trial i: the three numbers redrawn from the trial's start (a jump of
+        // 3 i steps from sb), the window moved past it.  A diffuse lane at its
+        // last bounce (n + 1 >= bounce_limit + mh) asks for no round: its new
+        // direction is never read (it redraws some trial and leaves the loop).
+        // (A wave-pooled form -- trials spread over the lanes with jumps of the
+        // state -- was bit-exact and slower: 12 % on C3 in round 2, 3.5 % in
+        // round 3, profiles/r03/ab_pool_trials.txt; the two-trial look-ahead
+        // bank this replaces: DESIGN.md s4.)
+        uint32_t sb = p.sb, mask = p.mask;
+        const bool wants = p.n + 1 < bounce_limit + p.mh;
+        bool need = wants & ((mask & (mask - 1u)) == 0u);    // nothing below the sentinel
+        if (__builtin_amdgcn_ballot_w64(need)) do {          // (do-while: no copies of the carried values)
             MM_LANE_STAT(kLpTrial);
-            // every lane draws (no branch: the loop is one block); a lane whose
-            // bank is full keeps its state (need = 1 implies bank = 0)
-            uint32_t t = p.seed;
-            rx = rand_pm1(t); ry = rand_pm1(t); rz = rand_pm1(t);
-            const float q2 = dot3(F3{rx, ry, rz}, F3{rx, ry, rz});
-            // accepted <=> !(q2 > 1 + 2^-23) <=> q2 < 1 + 2^-22 <=> the sign of the exact difference
-            // (q2 is finite) -- two pairable ops instead of a compare and a select
-            const uint32_t acc = __float_as_uint(q2 - 0x1.000004p0f) >> 31;
-            const uint32_t act = (bank >> 1) ^ 1u;  // bank < 2: still drawing
-            p.seed = act ? t : p.seed;
-            const uint32_t take = need & acc;
-            rd.x = take ? rx : rd.x;
-            rd.y = take ? ry : rd.y;
-            rd.z = take ? rz : rd.z;
-            len2 = take ? q2 : len2;
-            const uint32_t gain = (acc & act) - take;  // accepted on a lane that did not need it
-            p.s1 = gain > bank ? t : p.s1;              // the first banked trial's end
-            bank += gain;
-            need -= take;
-        } while (__builtin_amdgcn_ballot_w64(need != 0u));
-        p.bank = bank;
+            // a full window of rejected trials: skip them, empty the window
+            const bool full = mask == 1u << kTrialWindow;
+            sb = full ? sb * kLcgJump3.ac[2 * kTrialWindow] + kLcgJump3.ac[2 * kTrialWindow + 1] : sb;
+            mask = full ? 1u : mask;
+            const uint32_t d = 31u - (uint32_t)__clz((int)mask);  // trials drawn so far (mask != 0)
+            uint32_t t = lcg_jump_trials(sb, d);
+            const uint32_t acc = trial_accepted(t);
+            const uint32_t room = (mask >> kTrialWindow) ^ 1u;
+            mask += (room + (room & acc)) << (d & kTrialWindow);  // the sentinel moves up, bit d = acc
+            need &= (mask & (mask - 1u)) == 0u;
+        } while (__builtin_amdgcn_ballot_w64(need));
+        const uint32_t i = (uint32_t)__builtin_ctz(mask | (1u << kTrialWindow));
+        uint32_t s = lcg_jump_trials(sb, i);
+        const float rx = rand_pm1(s), ry = rand_pm1(s), rz = rand_pm1(s);
+        p.sb = s;
+        p.mask = (mask >> i) >> 1;  // (i = 31 only on a lane that leaves the loop)
+        const F3 rd = F3{rx, ry, rz};
+        const float len2 = dot3(rd, rd);
         const F3 rn = rsq(len2) * rd;                        // %358
         x = rn + side * nn;                                  // %367
     } else {

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(1024) void k_trace_mega(DevScene sc, TileJob job, S
 // resolve).
 
 // A deferred path's state (64 B: ori.xyz dir.x | dir.yz T.xy | T.z L.xyz |
-// seed, (n - mh) | mh << 15 | bank << 30, sample slot, s1) into / out of slot s of its block's tail
+// sb, (n - mh) | mh << 15, sample slot, mask: the trial window) into / out of slot s of its block's tail
 // ring.  kLdsPay (the deferral kernel with kRing = 2, chosen where the grid
 // image leaves room -- C3: 44 KB image + 34 KB static LDS per block, two
 // blocks per CU): the payload lives in the block's LDS beside the turn words,
@@ -176,8 +176,8 @@ __device__ __forceinline__ void tail_store(const TailQueue& q, uint32_t s, const
     const uint4 w2 = make_uint4(__float_as_uint(p.T.z), __float_as_uint(p.L.x), __float_as_uint(p.L.y),
                                 __float_as_uint(p.L.z));
     // (mh <= n and n - mh < bounce_limit <= 32767, mh < mirror_limit <= 32767: mm_runtime.hip checks the limits)
-    const uint32_t nmb = (uint32_t)(p.n - p.mh) | ((uint32_t)p.mh << 15) | (p.bank << 30);
-    const uint4 w3 = make_uint4(p.seed, nmb, slot, p.s1);
+    const uint32_t nm = (uint32_t)(p.n - p.mh) | ((uint32_t)p.mh << 15);
+    const uint4 w3 = make_uint4(p.sb, nm, slot, p.mask);
     if constexpr (kLdsPay) {
         uint4* r = ring_pay() + s;
         r[0] = w0; r[kTailRing] = w1; r[2 * kTailRing] = w2; r[3 * kTailRing] = w3;
@@ -201,11 +201,10 @@ __device__ __forceinline__ uint32_t tail_load(const TailQueue& q, uint32_t s, Pa
     p.dir = F3{__uint_as_float(a.w), __uint_as_float(b.x), __uint_as_float(b.y)};
     p.T = F3{__uint_as_float(b.z), __uint_as_float(b.w), __uint_as_float(c.x)};
     p.L = F3{__uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w)};
-    p.seed = d.x;
+    p.sb = d.x;
     p.mh = (int)((d.y >> 15) & 0x7FFFu);
     p.n = (int)(d.y & 0x7FFFu) + p.mh;
-    p.bank = d.y >> 30;
-    p.s1 = d.w;
+    p.mask = d.w;
     return d.z;
 }
 
@@ -502,21 +501,20 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             const uint32_t j = pix / job.w, i = pix - j * job.w;
             const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
             PathState p;
-            p.seed = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
+            p.sb = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
             if constexpr (kCams) {  // ori is not loop-invariant in a camera sequence
                 const mm_uniform cu = chunk_uniform(job, fr);
-                p.dir = jitter(primary_dir(cu, px, py), p.seed);
+                p.dir = jitter(primary_dir(cu, px, py), p.sb);
                 p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
             } else {
-                p.dir = jitter(primary_dir(job.u, px, py), p.seed);
+                p.dir = jitter(primary_dir(job.u, px, py), p.sb);
                 p.ori = ori;
             }
             p.T = F3{1.0f, 1.0f, 1.0f};
             p.L = F3{0.0f, 0.0f, 0.0f};
             p.n = 0;
             p.mh = 0;
-            p.bank = 0u;
-            p.s1 = 0u;
+            predraw_trials(p, job.predraw);
             bool overflow = false;
             bounce_loop<kStats>(sc, q, p, (int)job.e.bounce_limit, (int)job.e.mirror_limit, stack, c, overflow);
             if (overflow) atomicOr(err, kErrStack);
@@ -632,19 +630,20 @@ __device__ __forceinline__ uint32_t wavepersist_ring_body(const DevScene& sc, co
                 const uint32_t pix = path / spp, smp = path - pix * spp;
                 const uint32_t j = pix / job.w, i = pix - j * job.w;
                 const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
-                p.seed = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
+                p.sb = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
                 if constexpr (kCams) {
                     const mm_uniform cu = chunk_uniform(job, fr);
-                    p.dir = jitter(primary_dir(cu, px, py), p.seed);
+                    p.dir = jitter(primary_dir(cu, px, py), p.sb);
                     p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
                 } else {
-                    p.dir = jitter(primary_dir(job.u, px, py), p.seed);
+                    p.dir = jitter(primary_dir(job.u, px, py), p.sb);
                     p.ori = ori;
                 }
                 p.T = F3{1.0f, 1.0f, 1.0f};
                 p.L = F3{0.0f, 0.0f, 0.0f};
                 p.n = 0;
                 p.mh = 0;
+                predraw_trials(p, job.predraw);  // (tail chunks run none: their records carry the window)
                 slot = fr * n_paths + path;
             }
         }

@@ -51,6 +51,9 @@ VARIANTS = {
     "plain": (1, {26: 0}),          # MM_OPT_GRID_WIDE 0: plain 32-bit cell words (whole list per cell)
     "nomerge": (1, {24: 0}),        # MM_OPT_GRID_MERGE 0: cells along y by the rect size (round 2's grid)
     "grid-global-nomerge": (1, {1: 0, 24: 0}),
+    # MM_OPT_PREDRAW: trials a new-path chunk pre-draws per path (default 3 * bounce_limit, at most 31)
+    "predraw0": (1, {27: 0}), "predraw8": (1, {27: 8}), "predraw12": (1, {27: 12}), "predraw16": (1, {27: 16}),
+    "predraw20": (1, {27: 20}), "predraw24": (1, {27: 24}), "predraw28": (1, {27: 28}), "predraw31": (1, {27: 31}),
 }
 
 
