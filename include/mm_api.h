@@ -404,8 +404,15 @@ int  mm_set_pipeline(mm_ctx* ctx, int pipe);
                                   by mm_upload_scene */
 #define MM_OPT_PREDRAW    27  /* wave-persistent kernel: rejection-sampling trials a chunk of new paths draws
                                   per path before its bounces, acceptance only, into the path's trial window
-                                  (0..31; -1 default: 3 * bounce_limit, at most 31 -- 24 at 8 bounces,
-                                  scripts/predraw_model.py, profiles/predraw/).  Results never depend on it */
+                                  from its own stream (the pre-pass's own rounds; 0..31; -1 default: with
+                                  MM_OPT_PREDRAW_POOL 2 * (bounce_limit - 1) -- 14 at 8 bounces -- up to 24, else
+                                  3 * bounce_limit, at most 31; scripts/predraw_model.py,
+                                  scripts/predraw_pool_model.py, profiles/predraw/, profiles/pool/).  Results
+                                  never depend on it */
+#define MM_OPT_PREDRAW_POOL 28 /* wave-persistent kernel: 1 (default) after the own rounds the wave's lanes draw,
+                                  pooled, the further trials of the paths whose windows hold fewer accepted
+                                  trials than the path reads (cross-lane permutes; mm_trace.h pool_trials);
+                                  0 own rounds only.  Results never depend on it */
 #define MM_OPT_FAULT_INJECT 23 /* tests of the error path (results are then invalid): 0 off (default); 1 every
                                   wave-persistent launch raises an injected fault (error bit 3); 2 the tail
                                   rings' protocol waits give up at once (bit 2 when a wait was needed; a

@@ -106,6 +106,7 @@ struct mm_ctx {
     uint32_t* d_status = nullptr;
     mm::CallTracker calls;
     int opt_predraw = -1;        // MM_OPT_PREDRAW: trials pre-drawn per path at a chunk's start (-1: by the bounce limit)
+    bool opt_predraw_pool = true;  // MM_OPT_PREDRAW_POOL: pooled top-up rounds after the pre-pass's own rounds
     int opt_fault = 0;           // MM_OPT_FAULT_INJECT
     bool opt_grid_merge = true;  // MM_OPT_GRID_MERGE (read by mm_upload_scene)
     int opt_grid_cell = 100;     // MM_OPT_GRID_CELL (read by mm_upload_scene)

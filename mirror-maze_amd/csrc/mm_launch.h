@@ -91,6 +91,9 @@ struct TileJob {
     // window before its bounces (MM_OPT_PREDRAW, mm_plan.cpp; 0..31; mm_trace.h
     // predraw_trials).  Results never depend on it.
     uint32_t predraw = 0;
+    // Pooled top-up rounds after them (MM_OPT_PREDRAW_POOL; mm_trace.h pool_trials): the accepted trials a
+    // path's window should hold before its bounces, min(bounce_limit - 1, 31); 0: none.
+    uint32_t predraw_pool = 0;
     // Camera sequence (mm_trace_tile_cameras): frame f of the launch is traced with camera record f of this
     // device array (kCamStride floats per record: an mm_camera, padded to 64 B) instead of u.cam.  Null:
     // u.cam for every frame.  (Last member: the offsets of the fields above are those of the launches

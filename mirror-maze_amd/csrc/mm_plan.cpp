@@ -87,9 +87,27 @@ Choice choose_placement(const SceneFacts& f, const PlanOptions& o, int form) {
 // pre-pass at bounce_limit 8 near 22 trials with a flat minimum, and C3 measured fastest at 24 (1.865 ms/frame;
 // 20: 1.881, 28: 1.897, 16: 1.932, 31: 1.931, 0: 2.058 -- profiles/predraw/ab_k_sweep.txt): 3 b, capped by
 // the window's 31.
-uint32_t plan_predraw(int opt_predraw, uint32_t bounce_limit) {
+//
+// With the pooled top-up rounds (MM_OPT_PREDRAW_POOL, mm_trace.h pool_trials) the own rounds no longer pay
+// for the unluckiest of 64 lanes: they stop near the mean need and the pooled rounds serve the lanes still
+// short, each with a power-of-two share of the wave's lanes.  Below the mean most lanes are still short and
+// a share is one lane -- an own round at the pooled round's price (scripts/predraw_pool_model.py,
+// profiles/pool/model.txt: cheapest at bounce_limit 8 at 13..14 own rounds, 16 within 1 %, 12 within 4 %):
+// 2 (b - 1), the mean need rounded up (C3 measured: 13, 14, 16 and 18 within 0.5 % of each other, 12 0.7 %
+// and 10 2.3 % slower, profiles/pool/ab.txt).  The pooled rounds only fill the window's 31: past b = 13 the
+// mean need leaves them under 7 trials of room, the model's gain is gone by b = 16 (the N = 64 scene
+// measured 0.9 % slower at 30 own rounds), and the own rounds fill the window as before.
+uint32_t plan_predraw(int opt_predraw, bool pool, uint32_t bounce_limit) {
     if (opt_predraw >= 0) return std::min<uint32_t>((uint32_t)opt_predraw, 31u);
+    const uint64_t mean2 = 2ull * (bounce_limit ? bounce_limit - 1u : 0u);
+    if (pool && mean2 <= 24u) return (uint32_t)mean2;
     return (uint32_t)std::min<uint64_t>(3ull * bounce_limit, 31u);
+}
+// The accepted trials the pooled rounds top a window up to: what the path reads, b - 1 (its last bounce reads
+// none), at most the window's 31.  0: no pooled rounds.
+uint32_t plan_predraw_pool(bool pool, uint32_t bounce_limit) {
+    if (!pool || bounce_limit < 2u) return 0u;
+    return std::min<uint32_t>(bounce_limit - 1u, 31u);
 }
 
 LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mode, const size_t static_lds[2],
@@ -119,7 +137,8 @@ LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mo
                                   "method / LDS placement (grid search, or BVH form 7 with nodes + "
                                   "records in LDS)");
     LaunchPlan p;
-    p.predraw = plan_predraw(o.opt_predraw, e.bounce_limit);
+    p.predraw = plan_predraw(o.opt_predraw, o.opt_predraw_pool, e.bounce_limit);
+    p.predraw_pool = plan_predraw_pool(o.opt_predraw_pool, e.bounce_limit);
     p.defer = defer_built && (defer_on || wave) && (wave || tile_paths * n_frames >= o.opt_defer_min);
     // the deferral kernel's static LDS (tail ring, claimed queue ranges, and with ring kind 2 the rings'
     // 32 KB of records) must leave two 1024-thread blocks per CU: the records go to LDS where the

@@ -41,6 +41,7 @@ struct PlanOptions {
     int opt_defer = -1;
     uint32_t opt_defer_min = 1u << 24;
     int opt_predraw = -1;
+    bool opt_predraw_pool = true;
 };
 
 struct Choice {
@@ -66,6 +67,7 @@ struct LaunchPlan {
     bool fuse = false;   // resolve fused into the trace kernel
     uint32_t rows_per_batch = 0;
     uint32_t predraw = 0;  // trials a new-path chunk pre-draws per path (wave-persistent kernel)
+    uint32_t predraw_pool = 0;  // accepted trials the pooled rounds top a window up to (0: no pooled rounds)
     int code = MM_OK;    // else `error` is the text
     std::string error;
 };
@@ -73,8 +75,10 @@ constexpr size_t kNotBuilt = ~(size_t)0;
 // static_lds[k - 1]: the static LDS (sharedSizeBytes) of the deferral kernel with ring kind k, or kNotBuilt.
 // multi_fn: null for a single-frame call, else the name of the multi-frame entry point the call came through.
 // Trials a new-path chunk of the wave-persistent kernel draws into each path's window before its bounces
-// (MM_OPT_PREDRAW; -1: by the bounce limit).
-uint32_t plan_predraw(int opt_predraw, uint32_t bounce_limit);
+// (MM_OPT_PREDRAW; -1: by the bounce limit and by whether pooled rounds follow, MM_OPT_PREDRAW_POOL), and the
+// accepted trials those pooled rounds top each window up to (0: none).
+uint32_t plan_predraw(int opt_predraw, bool pool, uint32_t bounce_limit);
+uint32_t plan_predraw_pool(bool pool, uint32_t bounce_limit);
 LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mode, const size_t static_lds[2],
                      const mm_ext& e, uint32_t w, uint32_t h, uint32_t n_frames, const char* multi_fn);
 

@@ -86,6 +86,7 @@ PlanOptions plan_options(const mm_ctx* c) {
     o.opt_fuse = c->opt_fuse; o.opt_persist = c->opt_persist; o.opt_defer = c->opt_defer;
     o.opt_defer_min = c->opt_defer_min;
     o.opt_predraw = c->opt_predraw;
+    o.opt_predraw_pool = c->opt_predraw_pool;
     return o;
 }
 
@@ -449,6 +450,10 @@ int mm_set_option(mm_ctx* c, int key, int value) {
         case MM_OPT_PREDRAW:
             if (value < -1 || value > 31) return fail(c, MM_ERR_INVALID, "pre-drawn trials must be -1 (auto) or 0..31");
             c->opt_predraw = value;
+            return MM_OK;
+        case MM_OPT_PREDRAW_POOL:
+            if (value < 0 || value > 1) return fail(c, MM_ERR_INVALID, "pre-pass pooling must be 0 or 1");
+            c->opt_predraw_pool = value != 0;
             return MM_OK;
         case MM_OPT_FAULT_INJECT:
             if (value < 0 || value > 4) return fail(c, MM_ERR_INVALID, "fault inject must be 0..4");
@@ -925,6 +930,7 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
         job.cams = cams_dev;
         job.reserve_cus = c->opt_reserve_cus;
         job.predraw = plan.predraw;
+        job.predraw_pool = plan.predraw_pool;
         job.fault = (c->opt_fault == 1 || c->opt_fault == 4) ? (uint32_t)c->opt_fault : 0u;
         if (c->opt_fault == 2) job.ring_spin = 0;
         if (defer) {

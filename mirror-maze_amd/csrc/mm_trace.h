@@ -544,13 +544,73 @@ __device__ __forceinline__ uint32_t trial_accepted(uint32_t& s) {
 // The pre-pass of a new-path chunk: the first k trials of the path's stream
 // (after the primary jitter) drawn into its window at full lane utilisation,
 // acceptance only.  k (0..31) is wave-uniform; results never depend on it.
-__device__ __forceinline__ void predraw_trials(PathState& p, uint32_t k) {
+//
+// The own rounds cost every lane the unluckiest lane's trials.  With `need` > 0
+// (MM_OPT_PREDRAW_POOL; need = the accepted trials a path reads, at most the
+// window's 31) they stop early, at k = K1, and pooled rounds top up the lanes
+// still short -- "needy": fewer than `need` accepted bits below the sentinel,
+// and room in the window (a full window is never needy: the in-bounce rounds of
+// shade_step remain the backstop).  Bit i of a window is a pure function of
+// (sb, i), whichever lane computes it, so in a round
+//   - the active lanes are split stably, needy lanes (rank j by prefix popcount
+//     of their ballot) to lanes 0..n-1: one ds_permute carries each needy lane's
+//     stream state at its first undrawn trial d (a jump of d trials from sb) to
+//     lane j (the others' words land at n.. and are never used);
+//   - the n needy lanes get equal shares of S = 2^k lanes, the largest power of
+//     two with n S <= active lanes (at most 32 > the window): helper lane h
+//     fetches the state of needy rank h >> k with one ds_bpermute, jumps
+//     h & (S - 1) trials on and runs that trial's acceptance;
+//   - one ballot carries the accept bits back: the needy lane shifts its share
+//     out at j S, keeps the first m = min(S, 31 - d) bits (trials d .. d + m - 1,
+//     in order, no gaps: the window's invariant), ORs them in at d and moves the
+//     sentinel to d + m.  Trials past the window's end are computed and dropped.
+// The active lanes of a new-path chunk are a prefix of the wave (path < n_paths),
+// so a lane's rank among them is its lane id and every permute reads and writes
+// active lanes only (h >> k <= h; the split is a permutation of the prefix);
+// were they not a prefix the pooled stage is skipped.  Permutes go through the
+// LDS crossbar without an allocation.  Called under the chunk's live mask.
+__device__ __forceinline__ void pool_trials(uint32_t sb, uint32_t& mask, uint32_t need) {
+    const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+    if (act & (act + 1ull)) return;
+    const uint32_t n_act = (uint32_t)__builtin_popcountll(act);
+    const uint32_t lg_act = 31u - (uint32_t)__builtin_clz(n_act);
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    for (;;) {
+        const uint32_t d = 31u - (uint32_t)__clz((int)mask);  // trials drawn so far
+        // accepted bits = popcount - 1 (the sentinel)
+        const bool needy = ((uint32_t)__builtin_popcount(mask) <= need) & (d < kTrialWindow);
+        const uint64_t nb = __builtin_amdgcn_ballot_w64(needy);
+        if (!nb) break;
+        MM_LANE_STAT(kLpPool);
+        const uint32_t n = (uint32_t)__builtin_popcountll(nb);
+        uint32_t k = lg_act - (31u - (uint32_t)__builtin_clz(n));
+        k -= (n << k) > n_act ? 1u : 0u;  // the largest k with n 2^k <= active lanes
+        k = k > 5u ? 5u : k;
+        const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(nb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nb, 0u));
+        const uint32_t to = needy ? j : n + (lane - j);
+        const uint32_t sd = lcg_jump_trials(sb, d);
+        const uint32_t packed = (uint32_t)__builtin_amdgcn_ds_permute((int)(to << 2), (int)sd);
+        uint32_t t = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane >> k) << 2), (int)packed);
+        t = lcg_jump_trials(t, lane & ((1u << k) - 1u));
+        const uint64_t ab = __builtin_amdgcn_ballot_w64(trial_accepted(t) != 0u);
+        const uint32_t room = kTrialWindow - d, share = 1u << k;
+        const uint32_t m = room < share ? room : share;  // 1..31 on a needy lane
+        const uint32_t bits = (uint32_t)(ab >> ((j << k) & 63u)) & ((1u << m) - 1u);  // (& 63: other lanes' j)
+        const uint32_t at = d & kTrialWindow;
+        const uint32_t grown = (mask ^ (1u << at)) | (bits << at) | (1u << ((d + m) & kTrialWindow));
+        mask = needy ? grown : mask;
+    }
+}
+
+__device__ __forceinline__ void predraw_trials(PathState& p, uint32_t k, uint32_t need) {
     uint32_t s = p.sb, mask = 0u;
     for (uint32_t r = 0; r < k; ++r) {
         MM_LANE_STAT(kLpPredraw);
         mask |= trial_accepted(s) << r;
     }
-    p.mask = mask | (1u << k);
+    mask |= 1u << k;
+    if (need) pool_trials(p.sb, mask, need);
+    p.mask = mask;
 }
 
 // One shading step after a closest-hit query (the body of shaders.metal:306-340
@@ -598,7 +658,8 @@ __device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, flo
         // direction is never read (it redraws some trial and leaves the loop).
         // (A wave-pooled form -- trials spread over the lanes with jumps of the
         // state -- was bit-exact and slower: 12 % on C3 in round 2, 3.5 % in
-        // round 3, profiles/r03/ab_pool_trials.txt; the two-trial look-ahead
+        // round 3, profiles/r03/ab_pool_trials.txt; pooling the pre-pass's
+        // trials, once per path, is pool_trials above; the two-trial look-ahead
         // bank this replaces: DESIGN.md s4.)
         uint32_t sb = p.sb, mask = p.mask;
         const bool wants = p.n + 1 < bounce_limit + p.mh;

@@ -16,7 +16,7 @@ namespace mm {
 // exit.  Not a product build: the counting perturbs the timing.
 enum LanePhase : int {
     kLpChunk, kLpBounce, kLpGlobal, kLpGridIter, kLpRectTest, kLpCellStep, kLpCert, kLpFallback,
-    kLpShade, kLpDiffuse, kLpTrial, kLpMirror, kLpCertFull, kLpPredraw, kLpCount
+    kLpShade, kLpDiffuse, kLpTrial, kLpMirror, kLpCertFull, kLpPredraw, kLpPool, kLpCount
 };
 
 // Closest-hit query methods of the wave-persistent kernel (MM_OPT_TRAVERSAL):

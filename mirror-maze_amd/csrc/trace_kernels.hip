@@ -514,7 +514,7 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             p.L = F3{0.0f, 0.0f, 0.0f};
             p.n = 0;
             p.mh = 0;
-            predraw_trials(p, job.predraw);
+            predraw_trials(p, job.predraw, job.predraw_pool);
             bool overflow = false;
             bounce_loop<kStats>(sc, q, p, (int)job.e.bounce_limit, (int)job.e.mirror_limit, stack, c, overflow);
             if (overflow) atomicOr(err, kErrStack);
@@ -643,7 +643,7 @@ __device__ __forceinline__ uint32_t wavepersist_ring_body(const DevScene& sc, co
                 p.L = F3{0.0f, 0.0f, 0.0f};
                 p.n = 0;
                 p.mh = 0;
-                predraw_trials(p, job.predraw);  // (tail chunks run none: their records carry the window)
+                predraw_trials(p, job.predraw, job.predraw_pool);  // (tail chunks run none: their records carry the window)
                 slot = fr * n_paths + path;
             }
         }

@@ -9,7 +9,7 @@ from ._lib import (MM_EXT_ACCUMULATE, MM_EXT_COUNT_STATS, MM_EXT_RGBA8, MM_INFO_
                    MM_PIPE_REFERENCE, MM_PIPE_WAVEFRONT, MM_TRAV_AUTO, MM_TRAV_GRID, MM_TRAV_IFIF,
                    MM_TRAV_LEAF_INTERIOR, MM_TRAV_LEAN, MMError, lib, mm_camera, mm_ext, mm_stats, mm_uniform)
 from ._lib import (MM_INFO_GRID_LDS_CAP, MM_INFO_LAST_DEFER, MM_INFO_LAST_SCRATCH, MM_INFO_LAST_STATIC_LDS, MM_INFO_LAST_VGPRS,  # noqa: F401
-                   MM_OPT_FAULT_INJECT, MM_OPT_GRID_WIDE, MM_OPT_PREDRAW, MM_PENDING)
+                   MM_OPT_FAULT_INJECT, MM_OPT_GRID_WIDE, MM_OPT_PREDRAW, MM_OPT_PREDRAW_POOL, MM_PENDING)
 from ._lib import MM_INFO_GRID_CLASSES, MM_INFO_GRID_FLAT, MM_INFO_GRID_SLAB  # noqa: F401
 from ._lib import (MM_AOV_ID_FAILED, MM_AOV_ID_MIRROR_END, MM_AOV_ID_MISS, MM_AOV_ID_RECT, MM_AOV_ID_SURFACE,  # noqa: F401
                    mm_aov)

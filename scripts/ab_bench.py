@@ -54,6 +54,9 @@ VARIANTS = {
     # MM_OPT_PREDRAW: trials a new-path chunk pre-draws per path (default 3 * bounce_limit, at most 31)
     "predraw0": (1, {27: 0}), "predraw8": (1, {27: 8}), "predraw12": (1, {27: 12}), "predraw16": (1, {27: 16}),
     "predraw20": (1, {27: 20}), "predraw24": (1, {27: 24}), "predraw28": (1, {27: 28}), "predraw31": (1, {27: 31}),
+    "predraw10": (1, {27: 10}), "predraw13": (1, {27: 13}), "predraw14": (1, {27: 14}), "predraw18": (1, {27: 18}),
+    # MM_OPT_PREDRAW_POOL 0: own rounds only (3 * bounce_limit of them), the pre-pass before the pooled rounds
+    "nopool": (1, {28: 0}),
 }
 
 

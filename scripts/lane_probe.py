@@ -18,7 +18,7 @@ sys.path.insert(0, str(REPO / "mirror-maze_amd"))
 
 # mm_device.h LanePhase, in order
 PHASES = ["chunk", "bounce", "global_rect", "grid_iter", "rect_test", "cell_step", "certificate",
-          "bvh_fallback", "shade", "diffuse", "trial", "mirror", "certificate_full", "predraw"]
+          "bvh_fallback", "shade", "diffuse", "trial", "mirror", "certificate_full", "predraw", "pool"]
 RECORD = 49152  # mm_device.h kLaneStatRecord
 
 
