@@ -333,6 +333,66 @@ int  mm_accumulate_frames(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* c
                           uint32_t n_frames, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                           void* out_dev);
 
+/* ---- a pixel list, and topping up short histories ------------------------------
+ * mm_trace_pixels traces a caller-supplied SET of pixels of the frame, one
+ * launch (plus the resolve launch when the samples are staged), one camera
+ * (uni->cam), one frame: region-of-interest re-renders, progressive
+ * refinement, a few pixels of a large frame against an oracle, and extra
+ * samples for the pixels whose history mm_accumulate_frames left short.
+ *
+ * pixels_dev: DEVICE pointer, 8-byte aligned, n_pixels pairs (x, y) of uint32
+ * in view coordinates; stream-ordered -- the caller keeps it unchanged until
+ * the call has finished, the context makes no copy.  out_dev: n_pixels float4
+ * (16-byte aligned), or 4-byte RGBA8 pixels with MM_EXT_RGBA8; element e
+ * belongs to list entry e.  For an entry inside the view out[e] equals, on all
+ * bits, pixel (x, y) of mm_trace_tile with the same uni and ext: the same
+ * primary direction, RNG stream (pixel y*view_w + x, sample, ext->frame),
+ * bounce loop and summation order, for any spp in 1..4096.  MM_EXT_RGBA8: the
+ * texture-write conversion of that float4; MM_EXT_ACCUMULATE: out[e] += the
+ * value, alpha += 1; MM_EXT_COUNT_STATS fills stats as mm_trace_tile does
+ * (rays and paths exact).  The list's order is free; a pixel may appear more
+ * than once, and each entry gets its own, equal, result (with
+ * MM_EXT_ACCUMULATE each entry accumulates into its own element).  An entry
+ * with x >= view_w or y >= view_h is not traced: it writes (0, 0, 0, 0)
+ * (RGBA8: 0) or, with MM_EXT_ACCUMULATE, nothing, counts in neither paths nor
+ * rays, and is not an error.
+ *
+ * n_pixels = 0: MM_OK, nothing enqueued, no call number taken.  MM_ERR_INVALID:
+ * a null argument, a misaligned pointer, spp or the limits out of range (as in
+ * mm_trace_tile), MM_EXT_RGBA8 with MM_EXT_ACCUMULATE, n_pixels * spp (in
+ * chunks padded to 64) beyond the launch's 32-bit queue, or beyond the 2^29
+ * staged paths when the samples are staged (64 % spp != 0, MM_OPT_FUSE_RESOLVE
+ * 0 or MM_PIPE_REFERENCE).  MM_ERR_NO_SCENE without a scene; an earlier failed
+ * call is reported first.  Enqueued on the context's stream and numbered like
+ * the tile calls.  The launch never runs the mirror-tail rings (MM_OPT_DEFER
+ * and MM_OPT_DEFER_MIN select nothing, MM_INFO_LAST_DEFER reads 0 after it;
+ * MM_PIPE_WAVEFRONT: MM_ERR_UNSUPPORTED); MM_PIPE_REFERENCE is supported. */
+int  mm_trace_pixels(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
+                     const uint32_t* pixels_dev, uint64_t n_pixels,
+                     void* out_dev, mm_stats* stats);
+
+/* Extra samples into an accumulated frame, in place.  image_dev: w*h float4
+ * (16-byte aligned), the window (x0, y0, w, h) with y_stride 1 whose alpha is
+ * the history length N as mm_accumulate_frames writes it.  pixels_dev: the
+ * list (as above); extra_dev: n_pixels float4 (16-byte aligned), an
+ * mm_trace_pixels output for the same list.  m: the weight of the extra
+ * samples in frames (extra spp / frame spp), finite and > 0.
+ *
+ * All arithmetic is IEEE binary32, no contraction, in the order written; / is
+ * correctly rounded.  For entry e, (x, y) = pixels[e]:
+ *   skip the entry unless x0 <= x < x0 + w and y0 <= y < y0 + h
+ *   p = (y - y0)*w + (x - x0);  A = image[p];  E = extra[e];  Nn = A.a + m
+ *   image[p].c = A.c + ((E.c - A.c) * m) / Nn  (c = r, g, b);  image[p].a = Nn
+ * A list that names a window pixel twice leaves that pixel with one of the two
+ * results, unspecified which.
+ *
+ * MM_ERR_INVALID: a null context, image, list or extra_dev; a misaligned
+ * pointer; w or h 0, or w*h over 2^31 - 1; m not finite or not > 0; extra_dev
+ * overlapping image_dev.  n_pixels = 0: MM_OK.  Enqueued on the context's
+ * stream like mm_accumulate_frames; needs no uploaded scene. */
+int  mm_blend_pixels(mm_ctx* ctx, float* image_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                     const uint32_t* pixels_dev, const float* extra_dev, uint64_t n_pixels, float m);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

@@ -46,6 +46,9 @@ struct TileJob {
     // k_resolve's order; no per-sample staging buffer, no resolve launch.
     void* out = nullptr;  // float4 per pixel, or RGBA8 (4 B) with MM_EXT_RGBA8 (mm_wave_util.h store_pixel)
     uint32_t fuse = 0;
+    // 1: a pixel-list launch (mm_trace_pixels): `pixels` below names the pixels.  (In the padding ahead of
+    // wave_ts: every other member keeps the offset it had without it.)
+    uint32_t list = 0;
     // Diagnostics (mm_set_wave_timeline): per wave of the wave-persistent
     // kernel, 4 x u64 = (entry, LDS staged, exit, chunks) in wall_clock64()
     // ticks (100 MHz).  Null = off.
@@ -98,8 +101,19 @@ struct TileJob {
     // device array (kCamStride floats per record: an mm_camera, padded to 64 B) instead of u.cam.  Null:
     // u.cam for every frame.  (Last member: the offsets of the fields above are those of the launches
     // without it.)
-    const float* cams = nullptr;
+    //
+    // Pixel list (mm_trace_pixels, `list` set): the launch is w = n_pixels, h = 1, one camera, one frame, and
+    // entry e's pixel is record e of the device array `pixels`, (x, y) in view coordinates, instead of
+    // (x0 + i, y0 + j * y_stride); an entry outside the view is not traced (mm_wave_util.h list_pixel).  Read by
+    // the kList instances only.  A launch has cameras or a list, never both, and the two pointers share the
+    // slot: a member more would move the kernel arguments behind the job, and the camera-sequence instances'
+    // register allocation with them (profiles/pixels/kernel_resources.txt).
+    union {
+        const float* cams = nullptr;
+        const uint2* pixels;
+    };
 };
+static_assert(sizeof(TileJob) == 224, "the kernel-argument layout the tile instances were measured with");
 constexpr uint32_t kCamStride = 16;
 static_assert(sizeof(mm_camera) <= kCamStride * sizeof(float), "a camera record holds an mm_camera");
 
@@ -170,6 +184,17 @@ struct TpFrame {
     float n_max = 1.0f, tol_z = 0.0f, w_min = 0.0f;      // n_max as a float (exact: at most 65535)
 };
 hipError_t launch_temporal_frame(const TpFrame& frame, hipStream_t s);
+
+// mm_blend_pixels (temporal_kernels.hip): n list entries' extra samples into the accumulated window.
+struct TpBlend {
+    float4* image = nullptr;         // the window's w * h pixels (alpha = N), updated in place
+    const uint2* pixels = nullptr;   // n entries (x, y), view coordinates
+    const float4* extra = nullptr;   // n entries: the extra samples' mean (an mm_trace_pixels output)
+    uint64_t n = 0;                  // (n + 255) / 256 < 2^31
+    uint32_t x0 = 0, y0 = 0, w = 0, h = 0;  // w * h < 2^31
+    float m = 0.0f;                  // weight of the extra samples, in frames
+};
+hipError_t launch_blend_pixels(const TpBlend& blend, hipStream_t s);
 
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);

@@ -82,4 +82,12 @@ uint32_t plan_predraw_pool(bool pool, uint32_t bounce_limit);
 LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mode, const size_t static_lds[2],
                      const mm_ext& e, uint32_t w, uint32_t h, uint32_t n_frames, const char* multi_fn);
 
+// A pixel-list launch (mm_trace_pixels): n_pixels entries of e.spp samples in ONE launch, w = n_pixels, h = 1.
+// The list instances are the plain body's (no tail rings): never deferral, whatever MM_OPT_DEFER /
+// MM_OPT_DEFER_MIN say (MM_PIPE_WAVEFRONT, deferral always on, is refused); the resolve is fused iff
+// 64 % spp == 0 and MM_OPT_FUSE_RESOLVE, else the samples are staged.  MM_ERR_INVALID: the queue, n_pixels *
+// spp in chunks padded to 64, beyond the 32-bit counter (less the 2^24 the waves' last claims may overshoot),
+// or staged samples beyond kStagePathsMax.  rows_per_batch is 1.
+LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels);
+
 }  // namespace mm

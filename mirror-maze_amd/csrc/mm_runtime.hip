@@ -1011,6 +1011,134 @@ int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams,
     return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
 }
 
+int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
+                    void* out_dev, mm_stats* stats) {
+    if (!c) return MM_ERR_INVALID;
+    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
+    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_pixels: no scene uploaded");
+    if (n_pixels == 0) return MM_OK;
+    if (!u || !e || !pixels_dev || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_pixels: null argument");
+    // (the view, spp and the limits: the tile calls' checks, on a one-pixel tile)
+    if (int rc0 = check_tile(c, "mm_trace_pixels", u, e, e->mirror_limit, 0, 0, 1, 1, 1)) return rc0;
+    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
+    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
+        return fail(c, MM_ERR_INVALID, "mm_trace_pixels: MM_EXT_RGBA8 results cannot accumulate");
+    const size_t out_bpp = rgba8 ? 4 : 16;
+    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
+        return fail(c, MM_ERR_INVALID, std::string("mm_trace_pixels: list not 8-byte or output not ") +
+                                           std::to_string(out_bpp) + "-byte aligned");
+    HIPC(c, hipSetDevice(c->device));
+    const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
+    const bool persist = c->pipe != MM_PIPE_REFERENCE && c->opt_persist == 2;
+    const SceneFacts facts = scene_facts(c);
+    const PlanOptions opts = plan_options(c);
+    // the plan first: its refusals (the queue and staging bounds) need no kernel choice
+    const LaunchPlan plan = plan_pixels(opts, *e, n_pixels);
+    if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
+    int form = 0, mode = 0;
+    if (persist) {
+        Choice m = choose_method(facts, opts);
+        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
+        if (m.code != MM_OK) return fail(c, m.code, m.error);
+        form = m.form;
+        mode = m.mode;
+    }
+    const bool fuse = plan.fuse;
+    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_pixels * e->spp));
+    if (rc) return rc;
+    if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
+    if ((rc = begin_timing(c))) return rc;
+    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
+    const DevScene sc = dev_scene(c);
+    // the tile job of a one-row tile n_pixels wide, its pixels named by the list
+    TileJob job;
+    job.u = *u;
+    job.e = *e;
+    job.x0 = 0;
+    job.y0 = 0;
+    job.w = (uint32_t)n_pixels;
+    job.h = 1;
+    job.y_stride = 1;
+    job.view_w = (uint32_t)u->view_w;
+    job.fuse = fuse ? 1u : 0u;
+    job.wave_ts = c->d_wave_ts;
+    job.wave_ts_cap = c->wave_ts_cap;
+    job.out = out_dev;
+    job.reserve_cus = c->opt_reserve_cus;
+    job.predraw = plan.predraw;
+    job.predraw_pool = plan.predraw_pool;
+    job.fault = c->opt_fault == 1 ? 1u : 0u;
+    job.ring_diag = c->d_status + kStatusSlots;
+    job.list = 1;
+    job.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+    c->calls.begin_call();
+    rc = enqueue_launch(c, persist, [&](uint32_t* status, uint32_t launch_id) -> int {
+        job.status = status;
+        job.launch_id = launch_id;
+        if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
+        if (persist) {
+            c->last_form = form >= kFormGrid ? kFormGrid : form;
+            c->last_mode = mode;
+            c->last_kern_mode = mode;
+            c->last_kern_form = form;
+            c->last_kern_ring = 0;
+            HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev, c->d_work, want_stats, mode,
+                                             form, c->stream));
+        } else {
+            MegaOpts mo;
+            mo.reference = true;
+            mo.block = c->opt_block ? c->opt_block : 256u;
+            HIPC(c, launch_trace_mega(sc, job, c->d_samples, c->d_aux, err_dev, want_stats, mo, c->stream));
+        }
+        return MM_OK;
+    });
+    if (!rc && !fuse) {
+        const hipError_t re = launch_resolve(job, c->d_samples, job.out, c->stream);
+        if (re != hipSuccess) rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
+    }
+    c->last_defer = false;
+    char what[160] = "";
+    if (c->calls.call_has_launches())
+        snprintf(what, sizeof(what), "mm_trace_pixels, frame %u, %llu pixels, %u spp", e->frame,
+                 (unsigned long long)n_pixels, e->spp);
+    c->calls.end_call(what);
+    if (rc) return rc;
+    if ((rc = end_timing(c, fuse ? 1 : 2))) return rc;
+    if (want_stats) {
+        if ((rc = read_aux(c, stats))) return rc;
+        return report_failure(c, "");
+    }
+    return MM_OK;
+}
+
+int mm_blend_pixels(mm_ctx* c, float* image_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                    const uint32_t* pixels_dev, const float* extra_dev, uint64_t n_pixels, float m) {
+    // (argument checks first, and none of them needs the context, as in mm_accumulate_frames)
+    if (!image_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: null image");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7FFFFFFFull)
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: empty window or more than 2^31 - 1 pixels");
+    if (!(m > 0.0f) || !std::isfinite(m)) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: m must be positive and finite");
+    if (reinterpret_cast<uintptr_t>(image_dev) % 16) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: misaligned image");
+    if (n_pixels == 0) return c ? MM_OK : MM_ERR_INVALID;
+    if (!pixels_dev || !extra_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: null argument");
+    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(extra_dev) % 16)
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: misaligned buffer (float4: 16 bytes, the list: 8)");
+    if (n_pixels > (1ull << 38)) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: more entries than one launch holds");
+    if (ranges_overlap(image_dev, (uint64_t)w * h * 16, extra_dev, n_pixels * 16))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: extra_dev overlaps the image");
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    TpBlend b;
+    b.image = reinterpret_cast<float4*>(image_dev);
+    b.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+    b.extra = reinterpret_cast<const float4*>(extra_dev);
+    b.n = n_pixels;
+    b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
+    b.m = m;
+    HIPC(c, launch_blend_pixels(b, c->stream));
+    return MM_OK;
+}
+
 namespace {
 
 // Query policy of mm_query_rays / mm_trace_aov (aov_kernels.hip): the method the trace calls would take for

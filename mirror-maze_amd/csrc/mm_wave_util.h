@@ -50,6 +50,25 @@ __device__ __forceinline__ void store_pixel(const TileJob& job, void* __restrict
     }
 }
 
+// Entry pix of a pixel-list launch whose pixel lies outside the view (mm_trace_pixels): zero, or with
+// MM_EXT_ACCUMULATE nothing.
+__device__ __forceinline__ void store_unlisted(const TileJob& job, void* __restrict__ out, size_t pix) {
+    if (job.e.flags & MM_EXT_RGBA8)
+        reinterpret_cast<uint32_t*>(out)[pix] = 0u;
+    else if (!(job.e.flags & MM_EXT_ACCUMULATE))
+        reinterpret_cast<float4*>(out)[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// Entry `pix` (< job.w) of a pixel-list launch: its record, one 8-byte load, and whether the pixel lies in
+// the view.  Nothing is indexed by (px, py) unless this returns true; then py * view_w + px < 2^32 (a view is
+// at most 65536 x 65536).
+__device__ __forceinline__ bool list_pixel(const TileJob& job, uint32_t pix, uint32_t& px, uint32_t& py) {
+    const uint2 r = job.pixels[pix];
+    px = r.x;
+    py = r.y;
+    return r.x < job.view_w && r.y < (uint32_t)job.u.view_h;
+}
+
 // The pixel's mean, sum / spp: when spp = 2^k as sum * 2^-k (both are the
 // exact sum x 2^-k rounded once: the same float, without three IEEE divisions).
 __device__ __forceinline__ F3 pixel_mean(F3 acc, uint32_t spp) {

@@ -118,7 +118,30 @@ __global__ __launch_bounds__(256) void k_temporal_frame(const TpFrame a) {
     a.out[p] = o;
 }
 
+// mm_blend_pixels (include/mm_api.h): entry e's extra samples into its pixel of the accumulated window, in
+// place; one lane per entry.  An entry outside the window touches nothing (p is computed only inside it:
+// p < w * h < 2^31).
+__global__ __launch_bounds__(256) void k_blend_pixels(const TpBlend b) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= b.n) return;
+    const uint2 r = b.pixels[e];
+    if (r.x < b.x0 || r.x - b.x0 >= b.w || r.y < b.y0 || r.y - b.y0 >= b.h) return;
+    const uint32_t p = (r.y - b.y0) * b.w + (r.x - b.x0);
+    const float4 A = b.image[p];
+    const float4 E = b.extra[e];
+    const float Nn = A.w + b.m;
+    b.image[p] = make_float4(A.x + ((E.x - A.x) * b.m) / Nn, A.y + ((E.y - A.y) * b.m) / Nn,
+                             A.z + ((E.z - A.z) * b.m) / Nn, Nn);
+}
+
 }  // namespace
+
+hipError_t launch_blend_pixels(const TpBlend& blend, hipStream_t s) {
+    const uint64_t blocks = (blend.n + 255) / 256;
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_blend_pixels, dim3((unsigned)blocks), dim3(256), 0, s, blend);
+    return hipGetLastError();
+}
 
 hipError_t launch_temporal_frame(const TpFrame& frame, hipStream_t s) {
     TpFrame a = frame;

@@ -104,17 +104,23 @@ hipError_t launch_trace_chunks(const DevScene& sc, const mm_uniform& u, const ui
 // everywhere).  (The round-1 one-thread-per-path kernels over the production
 // BVH loop forms measured slower than the wave-persistent kernel and were
 // removed in round 6)
-template <bool kStats, typename Q>
+// kList (mm_trace_pixels): pixel pix is record pix of job.pixels; an entry outside the view runs no path.
+template <bool kStats, bool kList, typename Q>
 __device__ __forceinline__ void mega_body(const DevScene& sc, const Q& q, const TileJob& job,
                                           Sample* __restrict__ samples, unsigned long long* stats, uint32_t* err) {
     const uint32_t spp = job.e.spp;
     const uint32_t n_paths = job.w * job.h * spp;
     const uint32_t path = blockIdx.x * blockDim.x + threadIdx.x;
     Counters c;
-    if (path < n_paths) {
+    bool valid = path < n_paths;
+    uint32_t lx = 0, ly = 0;
+    if constexpr (kList) {
+        if (valid) valid = list_pixel(job, path / spp, lx, ly);
+    }
+    if (valid) {
         const uint32_t pix = path / spp, smp = path - pix * spp;
         const uint32_t j = pix / job.w, i = pix - j * job.w;
-        const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
+        const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
         uint32_t seed = seed_tile(py * job.view_w + px, smp, job.e.frame);
         const F3 d = jitter(primary_dir(job.u, px, py), seed);
         const F3 ori = F3{job.u.cam.center[0], job.u.cam.center[1], job.u.cam.center[2]};
@@ -125,13 +131,13 @@ __device__ __forceinline__ void mega_body(const DevScene& sc, const Q& q, const 
         if (overflow) atomicOr(err, 1u);
         samples[path] = s;
     }
-    if (kStats) flush_stats(stats, c, path < n_paths ? 1u : 0u);
+    if (kStats) flush_stats(stats, c, valid ? 1u : 0u);
 }
 
-template <bool kStats>
+template <bool kStats, bool kList = false>
 __global__ __launch_bounds__(1024) void k_trace_mega(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                      unsigned long long* stats, uint32_t* err) {
-    mega_body<kStats>(sc, RefQuery<kStats>{sc}, job, samples, stats, err);
+    mega_body<kStats, kList>(sc, RefQuery<kStats>{sc}, job, samples, stats, err);
 }
 
 // ---------------------------------------------------------------------------
@@ -469,7 +475,13 @@ __device__ __forceinline__ mm_uniform chunk_uniform(const TileJob& job, uint32_t
     return u;
 }
 
-template <bool kStats, bool kCams, typename Q>
+// Pixel-list launches (kList, mm_trace_pixels; w = n_pixels, h = 1, one frame): the pixel of queue slot
+// `path` is record path / spp of job.pixels instead of the tile's (x0 + i, y0 + j * y_stride) -- 8 B per lane,
+// spp consecutive lanes the same record, a chunk's 64 lanes at most 64 consecutive records --, consumed into
+// p.sb and p.dir before the bounce loop like the tile's.  A lane whose entry lies outside the view is not
+// valid: it runs nothing and counts nothing, and with the fused resolve its pixel's first lane writes the
+// entry's zero before the chunk's bounces (staged samples: the resolve kernel does).
+template <bool kStats, bool kCams, bool kList, typename Q>
 __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q& q, const TileJob& job,
                                                      Sample* __restrict__ samples, unsigned long long* stats,
                                                      uint32_t* err, uint32_t* work) {
@@ -494,12 +506,20 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
         const uint32_t qc = base >> 6;
         const uint32_t fr = job.n_frames > 1 ? qc / cpf : 0u;
         const uint32_t path = (qc - fr * cpf) * 64u + lane;
-        const bool valid = path < n_paths;
+        bool valid = path < n_paths;
+        uint32_t lx = 0, ly = 0;
+        if constexpr (kList) {
+            if (valid) {
+                const uint32_t e = path / spp;
+                valid = list_pixel(job, e, lx, ly);
+                if (!valid && job.fuse && path == e * spp) store_unlisted(job, job.out, e);
+            }
+        }
         F3 s = F3{0.0f, 0.0f, 0.0f};
         if (valid) {
             const uint32_t pix = path / spp, smp = path - pix * spp;
             const uint32_t j = pix / job.w, i = pix - j * job.w;
-            const uint32_t px = job.x0 + i, py = job.y0 + j * job.y_stride;
+            const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
             PathState p;
             p.sb = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
             if constexpr (kCams) {  // ori is not loop-invariant in a camera sequence
@@ -899,7 +919,9 @@ constexpr uint32_t kWpThreads = MM_WP_THREADS;
 // kRing: 0 no tail deferral; 1 tail rings, payload in global records; 2 tail rings, payload in LDS.
 // kCams: a camera-sequence launch (job.cams); the static-camera instances' code is the same with and without
 // the feature (gate: profiles/camera_sequence/kernel_resources.txt).
-template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false>
+// kList: a pixel-list launch (job.pixels, mm_trace_pixels), built for kRing = 0 and kCams = false only; the
+// tile instances' code is the same with and without the feature (gate: profiles/pixels/kernel_resources.txt).
+template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false, bool kList = false>
 __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersist(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                                unsigned long long* stats, uint32_t* err,
                                                                uint32_t* work) {
@@ -921,7 +943,7 @@ __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersis
         if constexpr (kRing != 0)
             return wavepersist_ring_body<kStats, kRing == 2, kCams>(sc, q, job, samples, stats, err, work);
         else
-            return wavepersist_body<kStats, kCams>(sc, q, job, samples, stats, err, work);
+            return wavepersist_body<kStats, kCams, kList>(sc, q, job, samples, stats, err, work);
     });
 #ifdef MM_LANE_STATS
     __syncthreads();  // every wave of the block is done: add its counts to the timeline buffer
@@ -960,9 +982,18 @@ static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, S
     const size_t lds = lds_static_grid(kLds) ? 0 : wavepersist_lds_bytes(sc, kLds);
     auto kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing>
                             : k_trace_wavepersist<false, kLds, kForm, kRing>;
-    if (job.cams)
+    if (job.list) {  // a pixel list: the plain body's instances, one frame
+        if constexpr (kRing == 0) {
+            if (job.n_frames != 1) return hipErrorInvalidValue;
+            kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, true>
+                               : k_trace_wavepersist<false, kLds, kForm, 0, false, true>;
+        } else {
+            return hipErrorInvalidValue;
+        }
+    } else if (job.cams) {
         kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing, true>
                            : k_trace_wavepersist<false, kLds, kForm, kRing, true>;
+    }
     const uint32_t grid =
         persistent_grid(kern, lds, job.reserve_cus, (uint64_t)job.w * job.h * job.e.spp * job.n_frames);
     if (!grid) return hipErrorInvalidValue;
@@ -1012,7 +1043,11 @@ hipError_t launch_trace_mega(const DevScene& sc, const TileJob& job, Sample* sam
     if (!o.reference) return hipErrorInvalidValue;  // one thread per path: MM_PIPE_REFERENCE only
     const uint32_t n = job.w * job.h * job.e.spp;
     const dim3 grid((n + o.block - 1) / o.block);
-    if (count_stats)
+    if (job.list && count_stats)
+        hipLaunchKernelGGL((k_trace_mega<true, true>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+    else if (job.list)
+        hipLaunchKernelGGL((k_trace_mega<false, true>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+    else if (count_stats)
         hipLaunchKernelGGL(k_trace_mega<true>, grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
     else
         hipLaunchKernelGGL(k_trace_mega<false>, grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
@@ -1022,9 +1057,19 @@ hipError_t launch_trace_mega(const DevScene& sc, const TileJob& job, Sample* sam
 // ---------------------------------------------------------------------------
 // Sample reduction: spp % 8 == 0 -> pairwise tree in blocks of 8, blocks added
 // left to right (the reference order for 64 spp); otherwise left to right.
+// kList (all three resolve kernels): the samples of a pixel-list launch (mm_trace_pixels); an entry whose
+// pixel lies outside the view has no samples and gets store_unlisted's zero.
+template <bool kList = false>
 __global__ void k_resolve(TileJob job, const Sample* __restrict__ samples, void* __restrict__ out) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= job.w * job.h) return;
+    if constexpr (kList) {
+        uint32_t lx, ly;
+        if (!list_pixel(job, pix, lx, ly)) {
+            store_unlisted(job, out, pix);
+            return;
+        }
+    }
     const uint32_t spp = job.e.spp;
     const Sample* s = samples + (size_t)pix * spp;
     F3 acc;
@@ -1046,11 +1091,20 @@ __global__ void k_resolve(TileJob job, const Sample* __restrict__ samples, void*
 // (64/spp whole pixels): every load is one coalesced 1-KB wave access, and
 // resolve_in_wave adds in k_resolve's order (bit-identical).  Used for spp 1,
 // 2, 4 (spp % 8 == 0 takes k_resolve8).
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_resolve_wave(TileJob job, const Sample* __restrict__ samples,
                                                       void* __restrict__ out) {
     const uint32_t n = job.w * job.h * job.e.spp;
     const uint32_t path = blockIdx.x * blockDim.x + threadIdx.x;  // waves never straddle the end: n % 64 == 0
-    const bool valid = path < n;                                   // unless the tile is ragged
+    bool valid = path < n;                                         // unless the tile is ragged
+    if constexpr (kList) {
+        if (valid) {
+            const uint32_t e = path / job.e.spp;
+            uint32_t lx, ly;
+            valid = list_pixel(job, e, lx, ly);
+            if (!valid && path == e * job.e.spp) store_unlisted(job, out, e);
+        }
+    }
     const Sample v = valid ? samples[path] : Sample{0.0f, 0.0f, 0.0f};
     resolve_in_wave(job, v, path, valid, out, 0);
 }
@@ -1059,10 +1113,18 @@ __global__ __launch_bounds__(256) void k_resolve_wave(TileJob job, const Sample*
 // 16-B loads (a pixel's samples are 96 B-aligned runs: 12 spp B per pixel),
 // added in k_resolve's tree -- no cross-lane shuffles, one active lane per
 // pixel instead of one in eight (mean: pixel_mean, mm_wave_util.h).
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_resolve8(TileJob job, const Sample* __restrict__ samples,
                                                   void* __restrict__ out) {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= job.w * job.h) return;
+    if constexpr (kList) {
+        uint32_t lx, ly;
+        if (!list_pixel(job, pix, lx, ly)) {
+            store_unlisted(job, out, pix);
+            return;
+        }
+    }
     const uint32_t spp = job.e.spp;
     const float4* q = reinterpret_cast<const float4*>(samples + (size_t)pix * spp);
     F3 acc;
@@ -1078,13 +1140,17 @@ __global__ __launch_bounds__(256) void k_resolve8(TileJob job, const Sample* __r
 
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s) {
     const uint32_t n = job.w * job.h;
+    const bool list = job.list != 0;
     if (job.e.spp % 8 == 0) {
-        hipLaunchKernelGGL(k_resolve8, dim3((n + 255) / 256), dim3(256), 0, s, job, samples, out);
+        hipLaunchKernelGGL(list ? k_resolve8<true> : k_resolve8<false>, dim3((n + 255) / 256), dim3(256), 0, s, job,
+                           samples, out);
     } else if (64 % job.e.spp == 0) {
         const uint32_t paths = n * job.e.spp;
-        hipLaunchKernelGGL(k_resolve_wave, dim3((paths + 255) / 256), dim3(256), 0, s, job, samples, out);
+        hipLaunchKernelGGL(list ? k_resolve_wave<true> : k_resolve_wave<false>, dim3((paths + 255) / 256), dim3(256),
+                           0, s, job, samples, out);
     } else {
-        hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, s, job, samples, out);
+        hipLaunchKernelGGL(list ? k_resolve<true> : k_resolve<false>, dim3((n + 255) / 256), dim3(256), 0, s, job,
+                           samples, out);
     }
     return hipGetLastError();
 }

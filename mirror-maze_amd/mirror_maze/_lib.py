@@ -143,6 +143,10 @@ EXPORTS = {
     "mm_accumulate_frames": (C.c_int, [P, C.POINTER(mm_uniform), P, P, C.POINTER(mm_aov), C.POINTER(mm_temporal_prev),
                                        C.POINTER(mm_temporal_params), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, P]),
+    "mm_trace_pixels": (C.c_int, [P, C.POINTER(mm_uniform), C.POINTER(mm_ext), P, C.c_uint64, P,
+                                  C.POINTER(mm_stats)]),
+    "mm_blend_pixels": (C.c_int, [P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, C.c_uint64,
+                                  C.c_float]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

@@ -413,6 +413,101 @@ class Renderer:
                                                w, h, out.data_ptr()))
         return out
 
+    # -- pixel lists -----------------------------------------------------------
+    def _pixel_list(self, pixels):
+        """The (n, 2) int32 CUDA tensor of a pixel list: `pixels` itself, or an
+        upload of an (n, 2) array of (x, y) pairs (int32 holds the bits of the
+        library's uint32)."""
+        import torch
+
+        dev = torch.device(f"cuda:{self.device}")
+        if not torch.is_tensor(pixels):
+            pixels = np.ascontiguousarray(pixels)
+            if pixels.dtype.kind not in "iu":
+                raise ValueError("pixels must hold integers")
+            pixels = torch.from_numpy(pixels.astype(np.uint32).view(np.int32).reshape(-1, 2)).to(dev)
+        if pixels.dtype == getattr(torch, "uint32", None):
+            pixels = pixels.view(torch.int32)
+        if not (pixels.is_cuda and pixels.dtype == torch.int32 and pixels.is_contiguous() and pixels.dim() == 2
+                and pixels.shape[1] == 2):
+            raise ValueError("pixels must be a contiguous int32 / uint32 (n, 2) CUDA tensor or an (n, 2) array")
+        return pixels
+
+    def trace_pixels(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, pixels, out=None, stats: bool = False,
+                     rgba8: bool = False):
+        """Trace a list of pixels (mm_trace_pixels).  `pixels`: an (n, 2) int32 /
+        uint32 CUDA tensor of (x, y) view coordinates, or an array that is
+        uploaded.  Entry e of the (n, 4) float32 result (`out` if given; uint8
+        RGBA8 with rgba8 / a uint8 `out`, as trace_tile) equals pixel (x, y) of
+        trace_tile with the same uniform and ext, bit for bit; an entry outside
+        the view gets zeros.  Returns (out, mm_stats or None)."""
+        import torch
+
+        pixels = self._pixel_list(pixels)
+        n = pixels.shape[0]
+        out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
+        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
+        st = _lib.mm_stats()
+        self._check(lib().mm_trace_pixels(self._ctx, C.byref(uniform), C.byref(e), pixels.data_ptr() if n else None,
+                                          n, out.data_ptr() if n else None, C.byref(st)))
+        return out, (st if stats else None)
+
+    def blend_pixels(self, image, pixels, extra, m: float, x0: int = 0, y0: int = 0):
+        """Blend extra samples into an accumulated frame, in place
+        (mm_blend_pixels).  `image`: the (h, w, 4) float32 CUDA tensor of the
+        window (x0, y0, w, h) whose alpha is the history length, as accumulate
+        returns it; `pixels`, `extra`: a pixel list and what trace_pixels
+        returned for it; `m`: the weight of the extra samples in frames (extra
+        spp / frame spp).  Entries outside the window are skipped; the list
+        must not name a window pixel twice.  Returns `image`."""
+        import torch
+
+        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
+                and image.dim() == 3 and image.shape[-1] == 4):
+            raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
+        pixels = self._pixel_list(pixels)
+        n = pixels.shape[0]
+        if not (torch.is_tensor(extra) and extra.is_cuda and extra.device == image.device
+                and extra.dtype == torch.float32 and extra.is_contiguous() and tuple(extra.shape) == (n, 4)):
+            raise ValueError(f"extra must be a contiguous float32 ({n}, 4) tensor on {image.device}")
+        h, w = image.shape[:2]
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
+        self._check(lib().mm_blend_pixels(self._ctx, image.data_ptr(), x0, y0, w, h, pixels.data_ptr() if n else None,
+                                          extra.data_ptr() if n else None, n, float(m)))
+        return image
+
+    def top_up(self, uniform: _lib.mm_uniform, camera, ext: _lib.mm_ext, acc, aov, n_min: float, extra_spp: int,
+               frame_key: int, x0: int = 0, y0: int = 0):
+        """Spend extra samples where an accumulated frame's history is short.
+        `acc`: ONE (h, w, 4) frame accumulate returned for the window (x0, y0,
+        w, h), traced with `camera` and `ext`; `aov`: that frame's guides (its
+        "id" buffer, (h, w) or (1, h, w)).  The pixels with history length
+        acc[..., 3] < n_min whose id is neither MM_AOV_ID_MISS nor
+        MM_AOV_ID_FAILED (those never get a history) are traced with extra_spp
+        samples each and blended into `acc` with weight extra_spp / ext.spp, in
+        place, in row-major order.  The extra samples are drawn with RNG frame
+        `frame_key`: pick a key outside the sequence's frame numbers, e.g.
+        2**20 + f for frame f, so that they are independent of every frame's
+        own samples.  Returns (acc, n_selected); nothing is launched when no
+        pixel is selected."""
+        ids = aov["id"] if isinstance(aov, dict) else aov
+        pixels = select_short_history(acc, ids, n_min, x0, y0)
+        n = int(pixels.shape[0])
+        if n == 0:
+            return acc, 0
+        u = _lib.mm_uniform.from_buffer_copy(bytes(uniform))
+        u.cam = _lib.mm_camera.from_buffer_copy(self._cameras([camera] if not isinstance(camera, np.ndarray)
+                                                              else camera.reshape(1, -1)).tobytes())
+        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
+                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        extra, _ = self.trace_pixels(u, e, pixels)
+        self.blend_pixels(acc, pixels, extra, extra_spp / ext.spp, x0, y0)
+        return acc, n
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the
@@ -447,6 +542,24 @@ class Renderer:
         ms, n = C.c_float(), C.c_uint32()
         self._check(lib().mm_last_timing(self._ctx, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def select_short_history(acc, ids, n_min: float, x0: int = 0, y0: int = 0):
+    """The pixel list Renderer.top_up traces: the pixels of the accumulated
+    window `acc` ((h, w, 4), alpha = history length) with alpha < n_min whose
+    `ids` entry ((h, w) or (1, h, w) int32, the guides' id buffer) is neither
+    MM_AOV_ID_MISS nor MM_AOV_ID_FAILED, as an (n, 2) int32 tensor of (x0 + i,
+    y0 + j) pairs in row-major order (torch.nonzero's: deterministic, no
+    duplicates) on acc's device.  Works on CPU tensors too."""
+    import torch
+
+    if acc.dim() != 3 or acc.shape[-1] != 4:
+        raise ValueError("acc must be one (h, w, 4) frame")
+    ids = ids.reshape(acc.shape[:2])
+    miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)  # the int32 with those bits
+    sel = (acc[..., 3] < n_min) & (ids != miss) & (ids != failed)
+    ji = torch.nonzero(sel)  # (n, 2) rows of (j, i), row-major
+    return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
 
 
 def make_ext(spp: int = 8, bounce_limit: int = 8, mirror_limit: int = 8, frame: int = 0,

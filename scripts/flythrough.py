@@ -12,6 +12,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 32 --frames 40 --aov aov/       # + feature buffers per frame
     python scripts/flythrough.py --maze 32 --frames 40 --denoise        # + frame_NNNN_dn.png beside each frame
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate     # + frame_NNNN_acc.png beside each frame
+    python scripts/flythrough.py --maze 32 --frames 40 --accumulate --top-up 2:24   # + extra samples where the history is short
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
@@ -30,6 +31,14 @@ Renderer.accumulate (mm_accumulate_frames, its defaults), the running mean of
 the frames before it wherever they showed the same surface point through the
 same mirrors; the history carries over from batch to batch.  With --denoise the
 denoiser then runs on the accumulated frames (frame_NNNN_dn.png).
+
+--top-up N[:SPP] (with --accumulate) tops every accumulated frame up to a history
+of N frames: the pixels whose history length is below N -- disoccluded by a turn
+or a step past a wall edge -- get SPP more samples each (default 3 x --spp)
+through Renderer.top_up (mm_trace_pixels + mm_blend_pixels), drawn with RNG frame
+2^20 + f.  The batch is then accumulated frame by frame, each frame's history
+being the topped-up frame before it, so the extra samples stay in the history;
+the share of pixels topped up is printed per frame.
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -75,10 +84,24 @@ def main(argv=None) -> int:
     ap.add_argument("--accumulate", action="store_true",
                     help="also write frame_NNNN_acc.png: the frame through Renderer.accumulate (temporal accumulation); "
                          "with --denoise the denoiser runs on the accumulated frames")
+    ap.add_argument("--top-up", metavar="N[:SPP]", default=None,
+                    help="with --accumulate: give the pixels whose history is shorter than N frames SPP more samples "
+                         "(default 3 x --spp) and blend them into the accumulated frame")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
         ap.error("--frames and --batch must be positive")
+    top_up = None  # (n_min, extra spp)
+    if a.top_up is not None:
+        if not a.accumulate:
+            ap.error("--top-up needs --accumulate")
+        try:
+            n_min, _, extra = a.top_up.partition(":")
+            top_up = (float(n_min), int(extra) if extra else 3 * a.spp)
+        except ValueError:
+            ap.error("--top-up takes N[:SPP]")
+        if not (top_up[0] > 1.0 and 1 <= top_up[1] <= 4096):
+            ap.error("--top-up: N must be above 1 and SPP in 1..4096")
 
     from mirror_maze import Player, Scene, walk_cameras
 
@@ -117,9 +140,21 @@ def main(argv=None) -> int:
                 continue
             bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
                                want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
-            if a.accumulate:
+            if a.accumulate and top_up:
+                # frame by frame: the history of frame k is the topped-up frame k - 1
+                acc_img = torch.empty_like(img)
+                for k in range(len(batch)):
+                    gk = {name: v[k:k + 1] for name, v in bufs.items()}
+                    r.accumulate(u, batch[k:k + 1], img[k:k + 1], gk, prev=prev, out=acc_img[k:k + 1])
+                    _, n_sel = r.top_up(u, batch[k], e, acc_img[k], gk, top_up[0], top_up[1], 2**20 + f0 + k)
+                    print(f"# frame {f0 + k}: topped up {n_sel} pixels ({100.0 * n_sel / (a.width * a.height):.2f} %) "
+                          f"with {top_up[1]} spp", flush=True)
+                    prev = (acc_img[k], gk, batch[k])
+                img = acc_img
+            elif a.accumulate:
                 img = r.accumulate(u, batch, img, bufs, prev=prev)
                 prev = (img[-1], {k: v[-1:] for k, v in bufs.items()}, batch[-1])
+            if a.accumulate:
                 acc = r.quantize(img).cpu().numpy()
                 r.sync()
                 for k in range(len(batch)):
