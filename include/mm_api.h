@@ -393,6 +393,56 @@ int  mm_trace_pixels(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
 int  mm_blend_pixels(mm_ctx* ctx, float* image_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                      const uint32_t* pixels_dev, const float* extra_dev, uint64_t n_pixels, float m);
 
+/* ---- per-pixel sample variance -------------------------------------------------
+ * The trace calls return each pixel's sample mean.  These two return, beside
+ * it, the sample variance of the pixel's luminance: how noisy the pixel is,
+ * for sampling where the noise is (Renderer.refine), for a stopping rule, and
+ * for a variance-guided filter.  The variance is taken where the samples
+ * already are: the calls always stage the samples (the path MM_OPT_FUSE_RESOLVE
+ * 0 takes, also at spp the plain calls would resolve in the wave), and the
+ * resolve that reads them for the mean takes their second moment with it.
+ *
+ * mm_trace_tile_var: out_dev is, on all bits, what the plain call writes for
+ * the same arguments -- mm_trace_tile for cams == NULL and n_frames == 1,
+ * mm_trace_tile_frames for cams == NULL, mm_trace_tile_cameras for cams !=
+ * NULL (a HOST array of n_frames cameras, consumed on return).
+ * mm_trace_pixels_var: out_dev is what mm_trace_pixels writes.  MM_EXT_RGBA8
+ * is allowed (out_dev then holds 4-byte pixels; var_dev does not change).
+ * var_dev: DEVICE pointer, 4-byte aligned, one float per pixel or list entry
+ * at out_dev's element index: f*w*h + j*w + i for a tile, e for a list.
+ *
+ * All arithmetic is IEEE binary32, no contraction, in the order written; / is
+ * correctly rounded.  s_0 .. s_{spp-1} are the pixel's samples, the ones the
+ * mean is taken of;
+ *   T(x) = the resolve's summation order: spp % 8 == 0: blocks of 8 summed as
+ *          ((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7)), the blocks added left to
+ *          right; otherwise x0 + x1 + ... left to right
+ *   l_k  = (0.25f*s_k.r + 0.5f*s_k.g) + 0.25f*s_k.b     (mm_denoise_frames' lum)
+ *   ml   = T(l) / (float)spp
+ *   q_k  = (l_k - ml) * (l_k - ml)
+ *   var  = T(q) / (float)(spp - 1)
+ * var is the unbiased sample variance of ONE sample's luminance; var / spp
+ * estimates the variance of the pixel's mean.  (Two passes over samples that
+ * lie in memory: no one-pass form and its cancellation.)  A list entry outside
+ * the view writes var = 0 (and out as mm_trace_pixels does).
+ *
+ * Every condition of the plain call with MM_OPT_FUSE_RESOLVE 0 applies: the
+ * 2^29 staged paths of a list or a multi-frame launch (a single frame beyond
+ * the staging bound is traced in row batches), the 2^32 queue, and a multi-frame
+ * launch needs tail deferral (it reports the plain call's error where the
+ * plan has none).  MM_ERR_INVALID in addition: spp < 2, MM_EXT_ACCUMULATE, a
+ * null or misaligned var_dev, var_dev overlapping out_dev.  n_pixels = 0:
+ * MM_OK, nothing enqueued.  Enqueued and numbered like the plain calls; the
+ * call tracker names them mm_trace_tile_var and mm_trace_pixels_var, and
+ * mm_last_timing counts two launches per row batch. */
+int  mm_trace_tile_var(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams,
+                       const mm_ext* ext, uint32_t n_frames,
+                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride,
+                       void* out_dev, float* var_dev, mm_stats* stats);
+int  mm_trace_pixels_var(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
+                         const uint32_t* pixels_dev, uint64_t n_pixels,
+                         void* out_dev, float* var_dev, mm_stats* stats);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

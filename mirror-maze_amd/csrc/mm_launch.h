@@ -198,5 +198,9 @@ hipError_t launch_blend_pixels(const TpBlend& blend, hipStream_t s);
 
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);
+// The same pixel, and the unbiased sample variance of the samples' luminance into var[pixel] (spp >= 2;
+// mm_trace_tile_var / mm_trace_pixels_var, include/mm_api.h).  var travels beside the job, as out does:
+// TileJob keeps the layout the trace kernels were measured with.
+hipError_t launch_resolve_var(const TileJob& job, const Sample* samples, void* out, float* var, hipStream_t s);
 
 }  // namespace mm

@@ -844,10 +844,25 @@ int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
 
 namespace {
 
+// The additional conditions of the variance calls (name: mm_trace_tile_var / mm_trace_pixels_var): at least
+// two samples, no accumulation, and a variance buffer of n floats apart from the output's out_bytes.
+int check_var(mm_ctx* c, const char* name, const mm_ext* e, const void* out_dev, uint64_t out_bytes,
+              const float* var_dev, uint64_t n) {
+    auto bad = [&](const char* what) { return fail(c, MM_ERR_INVALID, std::string(name) + ": " + what); };
+    if (e->spp < 2) return bad("a sample variance needs spp >= 2");
+    if (e->flags & MM_EXT_ACCUMULATE) return bad("MM_EXT_ACCUMULATE is not supported");
+    if (!var_dev) return bad("null var_dev");
+    if (reinterpret_cast<uintptr_t>(var_dev) % 4) return bad("var_dev not 4-byte aligned");
+    if (ranges_overlap(out_dev, out_bytes, var_dev, n * 4)) return bad("var_dev overlaps out_dev");
+    return MM_OK;
+}
+
 // cams: null, or the n_frames cameras of a camera-sequence launch (mm_trace_tile_cameras; u->cam is then unused)
+// var_call: mm_trace_tile_var -- the samples are staged whatever MM_OPT_FUSE_RESOLVE says, and the resolve
+// writes the per-pixel variance to var_dev beside the pixel
 int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
-                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev,
-                    mm_stats* stats) {
+                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, void* out_dev,
+                    mm_stats* stats, bool var_call = false, float* var_dev = nullptr) {
     if (!c) return MM_ERR_INVALID;
     // the multi-frame entry point this call came through (its conditions apply to a one-camera sequence too)
     const bool multi = n_frames > 1 || cams;
@@ -867,6 +882,11 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     if (reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
         return fail(c, MM_ERR_INVALID, std::string("mm_trace_tile: output not ") + std::to_string(out_bpp) +
                                            "-byte aligned");
+    if (var_call) {
+        // (elements in all, capped where the plan refuses the launch anyway: the byte counts fit 64 bits)
+        const uint64_t n_all = std::min<uint64_t>((uint64_t)w * h, (1ull << 40) / n_frames) * n_frames;
+        if (int rc0 = check_var(c, "mm_trace_tile_var", e, out_dev, n_all * out_bpp, var_dev, n_all)) return rc0;
+    }
     HIPC(c, hipSetDevice(c->device));
     const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
     const bool persist = c->pipe != MM_PIPE_REFERENCE && (c->pipe == MM_PIPE_WAVEFRONT || c->opt_persist == 2);
@@ -874,7 +894,8 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     // the plan (mm_plan.h): query method and LDS placement, then deferral / ring kind / fused resolve / rows
     // per launch, given the static LDS of the placement's deferral kernels
     const SceneFacts facts = scene_facts(c);
-    const PlanOptions opts = plan_options(c);
+    PlanOptions opts = plan_options(c);
+    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
     int form = 0, mode = 0;
     if (persist) {
         Choice m = choose_method(facts, opts);
@@ -969,7 +990,10 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
         // row batch), so one resolve over h x n_frames rows covers them all
         TileJob rj = job;
         if (defer) rj.h = job.h * n_frames;
-        const hipError_t re = launch_resolve(rj, c->d_samples, job.out, c->stream);
+        // (a later row batch's variances start at its own rows)
+        const hipError_t re =
+            var_call ? launch_resolve_var(rj, c->d_samples, job.out, var_dev + (size_t)j0 * w, c->stream)
+                     : launch_resolve(rj, c->d_samples, job.out, c->stream);
         if (re != hipSuccess) {
             rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
             break;
@@ -979,8 +1003,8 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     char what[160] = "";
     if (c->calls.call_has_launches())  // the launches this call enqueued (all of them unless rc)
         snprintf(what, sizeof(what), "%s, frames %u..%u, tile (%u, %u) %ux%u / %u, %u spp",
-                 multi ? fn : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0, y0, w, h, y_stride,
-                 e->spp);
+                 var_call ? "mm_trace_tile_var" : multi ? fn : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0,
+                 y0, w, h, y_stride, e->spp);
     c->calls.end_call(what);
     if (rc) return rc;
     if ((rc = end_timing(c, launches))) return rc;
@@ -1011,8 +1035,17 @@ int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams,
     return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
 }
 
-int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
-                    void* out_dev, mm_stats* stats) {
+int mm_trace_tile_var(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
+                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, void* out_dev, float* var_dev,
+                      mm_stats* stats) {
+    return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats, true, var_dev);
+}
+
+namespace {
+
+// var_call: mm_trace_pixels_var, as in trace_tile_impl
+int trace_pixels_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
+                      void* out_dev, mm_stats* stats, bool var_call, float* var_dev) {
     if (!c) return MM_ERR_INVALID;
     if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
     if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_pixels: no scene uploaded");
@@ -1027,11 +1060,18 @@ int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint3
     if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
         return fail(c, MM_ERR_INVALID, std::string("mm_trace_pixels: list not 8-byte or output not ") +
                                            std::to_string(out_bpp) + "-byte aligned");
+    if (var_call) {
+        if (n_pixels > 0xFFFFFFFFull)  // (the plan's own refusal, ahead of the byte counts below)
+            return fail(c, MM_ERR_INVALID, "mm_trace_pixels: more paths than one launch holds (2^32)");
+        if (int rc0 = check_var(c, "mm_trace_pixels_var", e, out_dev, n_pixels * out_bpp, var_dev, n_pixels))
+            return rc0;
+    }
     HIPC(c, hipSetDevice(c->device));
     const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
     const bool persist = c->pipe != MM_PIPE_REFERENCE && c->opt_persist == 2;
     const SceneFacts facts = scene_facts(c);
-    const PlanOptions opts = plan_options(c);
+    PlanOptions opts = plan_options(c);
+    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
     // the plan first: its refusals (the queue and staging bounds) need no kernel choice
     const LaunchPlan plan = plan_pixels(opts, *e, n_pixels);
     if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
@@ -1093,14 +1133,15 @@ int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint3
         return MM_OK;
     });
     if (!rc && !fuse) {
-        const hipError_t re = launch_resolve(job, c->d_samples, job.out, c->stream);
+        const hipError_t re = var_call ? launch_resolve_var(job, c->d_samples, job.out, var_dev, c->stream)
+                                       : launch_resolve(job, c->d_samples, job.out, c->stream);
         if (re != hipSuccess) rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
     }
     c->last_defer = false;
     char what[160] = "";
     if (c->calls.call_has_launches())
-        snprintf(what, sizeof(what), "mm_trace_pixels, frame %u, %llu pixels, %u spp", e->frame,
-                 (unsigned long long)n_pixels, e->spp);
+        snprintf(what, sizeof(what), "%s, frame %u, %llu pixels, %u spp",
+                 var_call ? "mm_trace_pixels_var" : "mm_trace_pixels", e->frame, (unsigned long long)n_pixels, e->spp);
     c->calls.end_call(what);
     if (rc) return rc;
     if ((rc = end_timing(c, fuse ? 1 : 2))) return rc;
@@ -1109,6 +1150,18 @@ int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint3
         return report_failure(c, "");
     }
     return MM_OK;
+}
+
+}  // namespace
+
+int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
+                    void* out_dev, mm_stats* stats) {
+    return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, false, nullptr);
+}
+
+int mm_trace_pixels_var(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
+                        void* out_dev, float* var_dev, mm_stats* stats) {
+    return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, true, var_dev);
 }
 
 int mm_blend_pixels(mm_ctx* c, float* image_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,

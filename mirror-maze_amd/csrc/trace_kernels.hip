@@ -8,6 +8,8 @@
 //                        blocks, waves pull 64-path chunks, pixels resolved in
 //                        the wave
 //   k_resolve            per-pixel sample reduction in the reference's order
+//   k_resolve_var        the same, with the sample variance of the pixel's luminance
+//                        (k_resolve8_var: spp % 8 == 0)
 #include <hip/hip_runtime.h>
 
 #include "grid_build.h"
@@ -1152,6 +1154,125 @@ hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, 
         hipLaunchKernelGGL(list ? k_resolve<true> : k_resolve<false>, dim3((n + 255) / 256), dim3(256), 0, s, job,
                            samples, out);
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The resolve with the per-pixel sample variance (mm_trace_tile_var, mm_trace_pixels_var; the definition:
+// include/mm_api.h).  The mean is accumulated by k_resolve's / k_resolve8's statements and stored through
+// store_pixel, so the pixel is theirs on all bits; beside it the samples' luminances are summed in the same
+// order T, and a second pass over the same samples sums the squared deviations from their mean, again in T.
+// var: one float per pixel, element pix (an entry of a list outside the view: 0).
+__device__ __forceinline__ float sample_lum(F3 s) { return (0.25f * s.x + 0.5f * s.y) + 0.25f * s.z; }
+
+// Every spp >= 2 with spp % 8 != 0: one thread per pixel, left to right, the samples read twice.
+template <bool kList = false>
+__global__ void k_resolve_var(TileJob job, const Sample* __restrict__ samples, void* __restrict__ out,
+                              float* __restrict__ var) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= job.w * job.h) return;
+    if constexpr (kList) {
+        uint32_t lx, ly;
+        if (!list_pixel(job, pix, lx, ly)) {
+            store_unlisted(job, out, pix);
+            var[pix] = 0.0f;
+            return;
+        }
+    }
+    const uint32_t spp = job.e.spp;
+    const Sample* s = samples + (size_t)pix * spp;
+    F3 acc = s[0];
+    float ls = sample_lum(s[0]);
+    for (uint32_t k = 1; k < spp; ++k) {
+        const F3 v = s[k];
+        acc = acc + v;
+        ls = ls + sample_lum(v);
+    }
+    store_pixel(job, out, pix, pixel_mean(acc, spp));
+    const float ml = ls / (float)spp;
+    const float d0 = sample_lum(s[0]) - ml;
+    float qs = d0 * d0;
+    for (uint32_t k = 1; k < spp; ++k) {
+        const float d = sample_lum(s[k]) - ml;
+        qs = qs + d * d;
+    }
+    var[pix] = qs / (float)(spp - 1u);
+}
+
+// The luminances of a block of 8 samples, read as k_resolve8 reads it: six 16-B loads.
+__device__ __forceinline__ void block_lums(const float4* __restrict__ q, float l[8]) {
+    const float4 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5];
+    l[0] = sample_lum(F3{a0.x, a0.y, a0.z}); l[1] = sample_lum(F3{a0.w, a1.x, a1.y});
+    l[2] = sample_lum(F3{a1.z, a1.w, a2.x}); l[3] = sample_lum(F3{a2.y, a2.z, a2.w});
+    l[4] = sample_lum(F3{a3.x, a3.y, a3.z}); l[5] = sample_lum(F3{a3.w, a4.x, a4.y});
+    l[6] = sample_lum(F3{a4.z, a4.w, a5.x}); l[7] = sample_lum(F3{a5.y, a5.z, a5.w});
+}
+// sum of (l_k - ml)^2 over a block of 8, in the block's tree
+__device__ __forceinline__ float block_sqdev(const float l[8], float ml) {
+    float d[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = (l[k] - ml) * (l[k] - ml);
+    return ((d[0] + d[1]) + (d[2] + d[3])) + ((d[4] + d[5]) + (d[6] + d[7]));
+}
+
+// spp % 8 == 0: one thread per pixel, k_resolve8's loads and tree.  spp == 8: the eight luminances stay in
+// registers between the passes (the samples are read once); spp > 8: the second pass reads the run again
+// (96 .. 768 B per pixel the thread itself has just read: L2 hits).
+template <bool kList = false>
+__global__ __launch_bounds__(256) void k_resolve8_var(TileJob job, const Sample* __restrict__ samples,
+                                                      void* __restrict__ out, float* __restrict__ var) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= job.w * job.h) return;
+    if constexpr (kList) {
+        uint32_t lx, ly;
+        if (!list_pixel(job, pix, lx, ly)) {
+            store_unlisted(job, out, pix);
+            var[pix] = 0.0f;
+            return;
+        }
+    }
+    const uint32_t spp = job.e.spp;
+    const float4* const q0 = reinterpret_cast<const float4*>(samples + (size_t)pix * spp);
+    const float4* q = q0;
+    F3 acc;
+    float ls = 0.0f, l[8];
+    for (uint32_t b = 0; b < spp; b += 8, q += 6) {
+        const float4 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3], a4 = q[4], a5 = q[5];
+        const F3 s0{a0.x, a0.y, a0.z}, s1{a0.w, a1.x, a1.y}, s2{a1.z, a1.w, a2.x}, s3{a2.y, a2.z, a2.w};
+        const F3 s4{a3.x, a3.y, a3.z}, s5{a3.w, a4.x, a4.y}, s6{a4.z, a4.w, a5.x}, s7{a5.y, a5.z, a5.w};
+        const F3 blk = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
+        acc = (b == 0) ? blk : acc + blk;
+        l[0] = sample_lum(s0); l[1] = sample_lum(s1); l[2] = sample_lum(s2); l[3] = sample_lum(s3);
+        l[4] = sample_lum(s4); l[5] = sample_lum(s5); l[6] = sample_lum(s6); l[7] = sample_lum(s7);
+        const float lb = ((l[0] + l[1]) + (l[2] + l[3])) + ((l[4] + l[5]) + (l[6] + l[7]));
+        ls = (b == 0) ? lb : ls + lb;
+    }
+    store_pixel(job, out, pix, pixel_mean(acc, spp));
+    const float ml = ls / (float)spp;
+    float qs = 0.0f;
+    if (spp == 8) {
+        qs = block_sqdev(l, ml);
+    } else {
+        q = q0;
+        for (uint32_t b = 0; b < spp; b += 8, q += 6) {
+            block_lums(q, l);
+            const float qb = block_sqdev(l, ml);
+            qs = (b == 0) ? qb : qs + qb;
+        }
+    }
+    var[pix] = qs / (float)(spp - 1u);
+}
+
+hipError_t launch_resolve_var(const TileJob& job, const Sample* samples, void* out, float* var, hipStream_t s) {
+    const uint32_t n = job.w * job.h;
+    const bool list = job.list != 0;
+    if (job.e.spp < 2) return hipErrorInvalidValue;
+    if (job.e.spp % 8 == 0)
+        hipLaunchKernelGGL(list ? k_resolve8_var<true> : k_resolve8_var<false>, dim3((n + 255) / 256), dim3(256), 0, s,
+                           job, samples, out, var);
+    else
+        hipLaunchKernelGGL(list ? k_resolve_var<true> : k_resolve_var<false>, dim3((n + 255) / 256), dim3(256), 0, s,
+                           job, samples, out, var);
     return hipGetLastError();
 }
 

@@ -508,6 +508,96 @@ class Renderer:
         self.blend_pixels(acc, pixels, extra, extra_spp / ext.spp, x0, y0)
         return acc, n
 
+    # -- per-pixel sample variance ------------------------------------------------
+    def trace_tile_var(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, x0: int, y0: int, w: int, h: int,
+                       y_stride: int = 1, cameras=None, n_frames: int = 1, out=None, var=None, stats: bool = False,
+                       rgba8: bool = False):
+        """A tile and the sample variance of each pixel's luminance
+        (mm_trace_tile_var).  `out` is what trace_tile (cameras None, n_frames
+        1), trace_tile_frames (cameras None) or trace_tile_cameras would return,
+        bit for bit: (h, w, 4), or (n_frames, h, w, 4) for a multi-frame call;
+        `var` is a float32 CUDA tensor of that shape without the last axis, the
+        unbiased variance of ONE sample's luminance (var / spp estimates the
+        pixel mean's).  ext.spp must be at least 2; the samples are staged
+        whatever MM_OPT_FUSE_RESOLVE says.  Returns (out, var, mm_stats or
+        None)."""
+        import torch
+
+        cams = None if cameras is None else self._cameras(cameras)
+        n = n_frames if cams is None else cams.shape[0]
+        lead = (h, w) if cams is None and n_frames == 1 else (n, h, w)
+        dev = f"cuda:{self.device}"
+        out, r8 = self._out(out, (*lead, 4), rgba8, dev)
+        if var is None:
+            var = torch.zeros(lead, dtype=torch.float32, device=dev)
+        if not (var.is_cuda and var.dtype == torch.float32 and var.is_contiguous() and tuple(var.shape) == lead):
+            raise ValueError(f"var must be a contiguous float32 CUDA tensor of shape {lead}")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
+        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
+        st = _lib.mm_stats()
+        self._check(lib().mm_trace_tile_var(self._ctx, C.byref(uniform), None if cams is None else cams.ctypes.data,
+                                            C.byref(e), n, x0, y0, w, h, y_stride, out.data_ptr(), var.data_ptr(),
+                                            C.byref(st)))
+        return out, var, (st if stats else None)
+
+    def trace_pixels_var(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, pixels, out=None, var=None,
+                         stats: bool = False, rgba8: bool = False):
+        """A pixel list and each entry's sample variance (mm_trace_pixels_var):
+        `out` as trace_pixels returns it, `var` an (n,) float32 CUDA tensor,
+        entry e the variance trace_tile_var gives that pixel, bit for bit; an
+        entry outside the view gets 0.  Returns (out, var, mm_stats or None)."""
+        import torch
+
+        pixels = self._pixel_list(pixels)
+        n = pixels.shape[0]
+        out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
+        if var is None:
+            var = torch.zeros((n,), dtype=torch.float32, device=pixels.device)
+        if not (var.is_cuda and var.dtype == torch.float32 and var.is_contiguous() and tuple(var.shape) == (n,)):
+            raise ValueError(f"var must be a contiguous float32 CUDA tensor of {n} elements")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
+        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
+        st = _lib.mm_stats()
+        self._check(lib().mm_trace_pixels_var(self._ctx, C.byref(uniform), C.byref(e),
+                                              pixels.data_ptr() if n else None, n, out.data_ptr() if n else None,
+                                              var.data_ptr() if n else None, C.byref(st)))
+        return out, var, (st if stats else None)
+
+    def refine(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, color, var, count, rel_tol: float, extra_spp: int,
+               frame_key: int, ids=None, x0: int = 0, y0: int = 0):
+        """One round of noise-driven sampling, in place.  `color` (h, w, 4),
+        `var` (h, w) and `count` (h, w) float32 CUDA tensors: the window (x0,
+        y0, w, h) as trace_tile_var returned it for `uniform` (its camera is
+        used) and the samples each pixel holds so far (ext.spp after the first
+        frame).  The pixels select_noisy names -- standard error of the mean
+        above rel_tol times the luminance; `ids`, a guides' id buffer, keeps
+        MISS / FAILED pixels out -- are traced with extra_spp (>= 2) samples
+        each by trace_pixels_var, and merge_samples pools both groups into
+        color[..., :3], var and count of those pixels; every other pixel keeps
+        its bits.  The extra samples are drawn with RNG frame `frame_key`: pick
+        a key outside the sequence's frame numbers, e.g. 2**20 + 64 * f + round
+        for round `round` of frame f, so that they are independent of every
+        frame's own samples and of the other rounds'.  The caller loops with a
+        new key per round until the return value, the number of pixels
+        selected, is small enough; nothing is launched for 0."""
+        pixels = select_noisy(color, var, count, rel_tol, ids=ids, x0=x0, y0=y0)
+        n = int(pixels.shape[0])
+        if n == 0:
+            return 0
+        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
+                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        mean_b, var_b, _ = self.trace_pixels_var(uniform, e, pixels)
+        j, i = (pixels[:, 1] - y0).long(), (pixels[:, 0] - x0).long()
+        mean, v, cnt = merge_samples(color[j, i, :3], var[j, i], count[j, i], mean_b[:, :3], var_b, float(extra_spp))
+        color[j, i, :3] = mean
+        var[j, i] = v
+        count[j, i] = cnt
+        return n
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the
@@ -560,6 +650,59 @@ def select_short_history(acc, ids, n_min: float, x0: int = 0, y0: int = 0):
     sel = (acc[..., 3] < n_min) & (ids != miss) & (ids != failed)
     ji = torch.nonzero(sel)  # (n, 2) rows of (j, i), row-major
     return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
+
+
+def _lum(c):
+    """The denoiser's luminance of (..., >= 3) colours."""
+    return (0.25 * c[..., 0] + 0.5 * c[..., 1]) + 0.25 * c[..., 2]
+
+
+def select_noisy(color, var, count, rel_tol: float, floor: float = 1e-3, ids=None, x0: int = 0, y0: int = 0):
+    """The pixel list Renderer.refine traces: the pixels of the window `color`
+    ((h, w, 4) or (h, w, 3)) whose mean's standard error, sqrt(var / count), is
+    above rel_tol * (lum(color) + floor) -- `var` (h, w) as trace_tile_var
+    returns it, `count` the samples per pixel, a scalar or an (h, w) tensor;
+    `floor` keeps black pixels from being selected for ever.  With `ids` ((h, w)
+    or (1, h, w) int32, a guides' id buffer) a pixel whose id is MM_AOV_ID_MISS
+    or MM_AOV_ID_FAILED is never selected.  Returns an (n, 2) int32 tensor of
+    (x0 + i, y0 + j) pairs in row-major order (torch.nonzero's: deterministic,
+    no duplicates) on color's device.  Works on CPU tensors too."""
+    import torch
+
+    if color.dim() != 3 or color.shape[-1] < 3:
+        raise ValueError("color must be one (h, w, 4) frame")
+    var = var.reshape(color.shape[:2])
+    if torch.is_tensor(count):
+        count = count.reshape(color.shape[:2])
+    sel = torch.sqrt(var / count) > rel_tol * (_lum(color) + floor)
+    if ids is not None:
+        ids = ids.reshape(color.shape[:2])
+        miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)
+        sel = sel & (ids != miss) & (ids != failed)
+    ji = torch.nonzero(sel)
+    return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
+
+
+def merge_samples(mean_a, var_a, n_a, mean_b, var_b, n_b):
+    """Pool two independent groups of samples of the same pixels: `mean_*`
+    (..., 3) colours, `var_*` (...) variances of one sample's luminance as
+    trace_tile_var / trace_pixels_var return them, `n_*` the samples in each
+    group (scalars or (...) tensors).  Returns (mean, var, n) of the n_a + n_b
+    samples together:
+      mean = mean_a + (mean_b - mean_a) * n_b / (n_a + n_b)          per channel
+      var  = ((n_a-1) var_a + (n_b-1) var_b
+              + n_a n_b / (n_a+n_b) * (lum(mean_a) - lum(mean_b))**2) / (n_a + n_b - 1)
+    Plain float32 torch operations, on the tensors' device: this is bookkeeping
+    over the pixels a round selected, not on the hot path, and stays in torch."""
+    import torch
+
+    n_a = torch.as_tensor(n_a, dtype=torch.float32, device=mean_a.device)
+    n_b = torch.as_tensor(n_b, dtype=torch.float32, device=mean_a.device)
+    n = n_a + n_b
+    mean = mean_a + (mean_b - mean_a) * n_b.unsqueeze(-1) / n.unsqueeze(-1)
+    d = _lum(mean_a) - _lum(mean_b)
+    var = ((n_a - 1.0) * var_a + (n_b - 1.0) * var_b + n_a * n_b / n * d ** 2) / (n - 1.0)
+    return mean, var, n
 
 
 def make_ext(spp: int = 8, bounce_limit: int = 8, mirror_limit: int = 8, frame: int = 0,

@@ -40,6 +40,17 @@ through Renderer.top_up (mm_trace_pixels + mm_blend_pixels), drawn with RNG fram
 being the topped-up frame before it, so the extra samples stay in the history;
 the share of pixels topped up is printed per frame.
 
+--refine TOL[:SPP[:ROUNDS]] also writes frame_NNNN_ref.png beside each frame: the
+frame after up to ROUNDS (default 2) rounds of Renderer.refine, each giving the
+pixels whose mean's standard error is above TOL times their luminance SPP more
+samples (default 3 x --spp) through mm_trace_pixels_var, drawn with RNG frame
+2^20 + 64 f + round.  The frames are then traced one by one through
+Renderer.trace_tile_var (mm_trace_tile_var: the frame and its per-pixel sample
+variance); the share of pixels each round took is printed per frame.  With
+--denoise the denoiser runs on the refined frames.  Not with --accumulate: a
+history of frames with unequal sample counts is not what mm_accumulate_frames
+averages.
+
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
 """
@@ -87,6 +98,9 @@ def main(argv=None) -> int:
     ap.add_argument("--top-up", metavar="N[:SPP]", default=None,
                     help="with --accumulate: give the pixels whose history is shorter than N frames SPP more samples "
                          "(default 3 x --spp) and blend them into the accumulated frame")
+    ap.add_argument("--refine", metavar="TOL[:SPP[:ROUNDS]]", default=None,
+                    help="also write frame_NNNN_ref.png: up to ROUNDS (default 2) rounds of SPP more samples (default "
+                         "3 x --spp) for the pixels whose standard error is above TOL times their luminance")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
@@ -102,6 +116,20 @@ def main(argv=None) -> int:
             ap.error("--top-up takes N[:SPP]")
         if not (top_up[0] > 1.0 and 1 <= top_up[1] <= 4096):
             ap.error("--top-up: N must be above 1 and SPP in 1..4096")
+    refine = None  # (rel_tol, extra spp, rounds)
+    if a.refine is not None:
+        if a.accumulate:
+            ap.error("--refine does not go with --accumulate")
+        try:
+            parts = a.refine.split(":")
+            if not 1 <= len(parts) <= 3:
+                raise ValueError
+            refine = (float(parts[0]), int(parts[1]) if len(parts) > 1 and parts[1] else 3 * a.spp,
+                      int(parts[2]) if len(parts) > 2 else 2)
+        except ValueError:
+            ap.error("--refine takes TOL[:SPP[:ROUNDS]]")
+        if not (refine[0] > 0.0 and 2 <= refine[1] <= 4096 and 1 <= refine[2] <= 64 and a.spp >= 2):
+            ap.error("--refine: TOL must be positive, SPP in 2..4096, ROUNDS in 1..64, and --spp at least 2")
 
     from mirror_maze import Player, Scene, walk_cameras
 
@@ -117,26 +145,55 @@ def main(argv=None) -> int:
     import numpy as np
     import torch
 
-    from mirror_maze import Renderer, make_ext
+    from mirror_maze import Renderer, make_ext, mm_camera, mm_uniform
     from mirror_maze.io import quantize, write_png
 
     out_dir = Path(a.out)
     out_dir.mkdir(parents=True, exist_ok=True)
     u = player.uniform()  # view size and chunk width; its camera is not used
-    floats = a.denoise or a.accumulate  # the batch is traced as float frames
+    floats = a.denoise or a.accumulate or refine is not None  # the batch is traced as float frames
     prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera
     with Renderer(0) as r:
         r.upload_scene(scene)
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
-            img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not floats)
+            if refine:
+                # frame by frame (a single-frame variance call runs at any size; frame k is the batch launch's)
+                img = torch.empty((len(batch), a.height, a.width, 4), dtype=torch.float32, device="cuda:0")
+                var = torch.empty((len(batch), a.height, a.width), dtype=torch.float32, device="cuda:0")
+                us = []
+                for k in range(len(batch)):
+                    uk = mm_uniform.from_buffer_copy(u)
+                    uk.cam = mm_camera.from_buffer_copy(np.ascontiguousarray(batch[k], dtype=np.float32).tobytes())
+                    us.append(uk)
+                    r.trace_tile_var(uk, make_ext(a.spp, a.bounces, a.mirrors, frame=f0 + k), 0, 0, a.width, a.height,
+                                     out=img[k], var=var[k])
+            else:
+                img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not floats)
             frames = (r.quantize(img) if floats else img).cpu().numpy()
             r.sync()
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
-            print(f"# frames {f0}..{f0 + len(batch) - 1}: one launch, {out_dir}/frame_{f0:04d}.png ...", flush=True)
-            if a.aov is None and not floats:
+            print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if refine else 'one launch'}, "
+                  f"{out_dir}/frame_{f0:04d}.png ...", flush=True)
+            if refine:
+                for k in range(len(batch)):
+                    count = torch.full((a.height, a.width), float(a.spp), dtype=torch.float32, device="cuda:0")
+                    shares = []
+                    for rnd in range(refine[2]):
+                        n_sel = r.refine(us[k], e, img[k], var[k], count, refine[0], refine[1],
+                                         2**20 + 64 * (f0 + k) + rnd)
+                        shares.append(f"{100.0 * n_sel / (a.width * a.height):.2f} %")
+                        if n_sel == 0:
+                            break
+                    print(f"# frame {f0 + k}: refined with {refine[1]} spp per round, pixels per round: "
+                          f"{', '.join(shares)}", flush=True)
+                done = r.quantize(img).cpu().numpy()
+                r.sync()
+                for k in range(len(batch)):
+                    write_png(out_dir / f"frame_{f0 + k:04d}_ref.png", done[k])
+            if a.aov is None and not (a.denoise or a.accumulate):
                 continue
             bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
                                want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
