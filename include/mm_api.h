@@ -258,6 +258,62 @@ int  mm_denoise_frames(mm_ctx* ctx, const float* color_dev, const mm_aov* guides
                        const mm_denoise_params* p, uint32_t n_frames,
                        uint32_t w, uint32_t h, void* out_dev);
 
+/* ---- variance-guided denoising -------------------------------------------------
+ * The same a-trous filter with the luminance stop of every pixel scaled by the
+ * local standard deviation of the pixel MEAN (the SVGF form), for frames whose
+ * noise is uneven: mirror chains, or pixels that mm_trace_pixels_var topped up
+ * to different sample counts.  The variance is carried through the passes with
+ * squared weights and the last pass's is returned, so a caller can stop, refine
+ * again or composite with it.
+ *
+ * color_dev, guides, out_dev: exactly as in mm_denoise_frames (frame-major, tile
+ * index space; a tap never reads another frame; MM_DNV_RGBA8 for an RGBA8
+ * out_dev).  vmean_dev: n_frames*w*h floats (4-byte aligned), the variance of
+ * the pixel mean's luminance: var / count of mm_trace_tile_var, or of the merged
+ * (var, count) after extra samples.  var_out_dev: n_frames*w*h floats (4-byte
+ * aligned) or NULL: the variance image of the last pass.
+ *
+ * All arithmetic is IEEE binary32 (subnormals kept), no contraction, in the
+ * order written; / and sqrtf are correctly rounded.  hk[5] and lum as in
+ * mm_denoise_frames; k3[3] = {1/4, 1/2, 1/4}; C, V are the pass's input colour
+ * and variance (color_dev and vmean_dev for pass 0, else the previous pass's
+ * outputs); for pass i: s = 1 << i.  same(p,q):
+ *   id_q == id_p (all 32 bits)  and  al_q.w == al_p.w  and
+ *   (nd_p.x*nd_q.x + nd_p.y*nd_q.y) + nd_p.z*nd_q.z >= 0.
+ * For pixel p = (x, y):
+ *   if sigma_l > 0:      (this pixel's stop: a 3x3 of V at unit spacing in every pass)
+ *     GV = 0; GW = 0
+ *     for dy = -1..1 (outer), dx = -1..1 (inner):
+ *       q = (x+dx, y+dy); skip q outside [0,w) x [0,h)
+ *       unless dx == 0 && dy == 0, skip q unless same(p,q)
+ *       g = k3[dy+1] * k3[dx+1];  GV = GV + g * V_q;  GW = GW + g
+ *     slp = sigma_l * sqrtf(GV / GW) + eps_l
+ *   S = (0,0,0); W = 0; SV = 0
+ *   for dy = -2..2 (outer), dx = -2..2 (inner):
+ *     q = (x + s*dx, y + s*dy); skip q outside [0,w) x [0,h)
+ *     unless dx == 0 && dy == 0, skip q unless same(p,q)
+ *     g = hk[dy+2] * hk[dx+2]
+ *     if sigma_z > 0: t = (nd_p.w - nd_q.w) / (sigma_z * (nd_p.w + nd_q.w)); g = g / (1.0f + t*t)
+ *     if sigma_l > 0: t = (lum(p) - lum(q)) / slp;                           g = g / (1.0f + t*t)
+ *     S.c = S.c + g * C_q.c  (c = r, g, b);  W = W + g;  SV = SV + (g * g) * V_q
+ *   out.rgb = S / W;  out.a = C_p.a;  Vout = SV / (W * W)
+ * (defined for what mm_denoise_frames is, and finite V >= 0).  With sigma_l <= 0
+ * the colour is, on all bits, mm_denoise_frames' with the same n_passes and
+ * sigma_z and sigma_l = 0; with both terms off Vout is a fixed linear filter of V.
+ * Vout treats the taps as independent: later passes' taps share inputs, so it
+ * understates the variance of a several-pass result.
+ *
+ * MM_ERR_INVALID: everything mm_denoise_frames rejects; a null or misaligned
+ * vmean_dev; a misaligned var_out_dev; sigma_l > 0 with eps_l not finite or not
+ * > 0; unknown flags; reserved != 0; out_dev or var_out_dev overlapping an
+ * input or each other.  Enqueued like mm_denoise_frames, whose scratch (and a
+ * variance image per intermediate) it shares: calls of the two, on one stream
+ * or several, take turns in the order they were made, without a host wait. */
+int  mm_denoise_frames_var(mm_ctx* ctx, const float* color_dev, const mm_aov* guides,
+                           const float* vmean_dev, const mm_denoise_var_params* p,
+                           uint32_t n_frames, uint32_t w, uint32_t h,
+                           void* out_dev, float* var_out_dev);
+
 /* ---- temporal accumulation through mirror chains -----------------------------
  * Carries a history through the frames of a camera sequence: every surface of
  * the scene is matte or a perfect planar mirror, so the radiance a pixel shows

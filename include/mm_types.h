@@ -109,6 +109,18 @@ typedef struct mm_denoise_params {   /* 16 bytes */
     uint32_t flags;     /* MM_DN_RGBA8 */
 } mm_denoise_params;
 
+/* Parameters of mm_denoise_frames_var (mm_api.h): the same filter with its
+ * luminance stop scaled per pixel by the standard deviation of the pixel mean. */
+#define MM_DNV_RGBA8 1u   /* the output is RGBA8 (4 B per pixel), not float4  */
+typedef struct mm_denoise_var_params {   /* 24 bytes */
+    uint32_t n_passes;  /* 1..MM_DENOISE_MAX_PASSES; pass i spaces its 5x5 taps 2^i apart */
+    float    sigma_z;   /* depth term; <= 0: off (as mm_denoise_params) */
+    float    sigma_l;   /* luminance stop in standard deviations; <= 0: off.  NOT halved per pass */
+    float    eps_l;     /* added to the stop; finite and > 0 when sigma_l > 0, else ignored */
+    uint32_t flags;     /* MM_DNV_RGBA8 */
+    uint32_t reserved;  /* 0 */
+} mm_denoise_var_params;
+
 /* Parameters of mm_accumulate_frames (mm_api.h): temporal accumulation of a
  * camera sequence's frames, the history reprojected through the mirror chains. */
 typedef struct mm_temporal_params {   /* 16 bytes */

@@ -24,13 +24,14 @@
 //          the frame or rejected by the key test is computed and not added
 //          (a select, not a zero weight: the accumulators never see it).
 //          Quotients are Markstein's over a correctly rounded reciprocal
-//          (dn_div below, 6 operations), which are RN(a / d) inside exponent
+//          (dn_div, mm_denoise.h, 6 operations), which are RN(a / d) inside exponent
 //          ranges that a taken tap's operands leave only for odd inputs.
 //   exact  where some taken tap of the pixel was outside those ranges, the
 //          pixel is computed again by a plain loop with IEEE division, and
 //          that result is stored.
 #include <hip/hip_runtime.h>
 
+#include "mm_denoise.h"
 #include "mm_launch.h"
 #include "mm_trace.h"
 
@@ -38,63 +39,11 @@ namespace mm {
 
 namespace {
 
-__device__ __forceinline__ float dn_lum(const float4& c) { return (0.25f * c.x + 0.5f * c.y) + 0.25f * c.z; }
-
 __global__ void k_denoise_keys(const float4* __restrict__ al, const uint32_t* __restrict__ id,
                                uint2* __restrict__ keys, size_t n) {
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
         keys[i] = make_uint2(id[i], __float_as_uint(al[i].w));
-}
-
-// The key of pixel i: (id, al.w).  Two keys are equal when the ids are (all 32 bits) and the al.w are as floats.
-__device__ __forceinline__ void dn_key(const DnPass& a, uint32_t i, uint32_t& id, float& mh) {
-    const uint2 k = a.keys[i];
-    id = k.x;
-    mh = __uint_as_float(k.y);
-}
-
-// RN(a / d) without the compiler's IEEE division sequence: Markstein's quotient over y = RN(1/d) (mm_trace.h
-// qdiv, rcp_guarded: 6 operations instead of ~12).  It is the correctly rounded quotient when nothing under- or
-// overflows on the way.  The conditions used here, with room to spare:
-//   dn_den_ok  |d| in [2^-40, 2^40]          (rcp_guarded's verified range is [2^-44, 2^44]);
-//   dn_num_ok  a = 0 or |a| in [2^-60, 2^60];
-// then |a / d| lies in [2^-100, 2^100] and the exact residual a - q*d, whose lowest bit is above 2^-48 |a|, is a
-// normal float.  A NaN fails either test.  A zero numerator gives a zero (its sign may differ from IEEE's; both
-// quotients t below are used as t * t only) or, over a denominator whose reciprocal is not finite, a NaN, which
-// the test of 1 + t*t then catches.  The weights g need no test: they start as 2^-8 .. 9/64 and are divided at
-// most twice by an f in [1, 2^40].
-__device__ __forceinline__ bool dn_den_ok(float d) {
-    bool ok = fabsf(d) >= 0x1p-40f;
-    ok &= fabsf(d) <= 0x1p40f;
-    return ok;
-}
-__device__ __forceinline__ bool dn_num_ok(float a) {
-    bool ok = fabsf(a) >= 0x1p-60f;
-    ok &= fabsf(a) <= 0x1p60f;
-    ok |= a == 0.0f;
-    return ok;
-}
-__device__ __forceinline__ float dn_div(float a, float d) { return qdiv(a, d, rcp_guarded(d)); }
-
-struct DnPixel {
-    float4 C, nd;   // the centre's colour and (normal, distance)
-    uint32_t id;    // its key
-    float mh;
-    float lum;
-    uint32_t x, y;  // in the frame (w * h < 2^31: mm_denoise_frames)
-};
-
-// Whether tap q shows the centre's surface (the three-clause test of the specification).
-__device__ __forceinline__ bool dn_same_surface(const DnPass& a, const DnPixel& c, uint32_t q, const float4& ndq) {
-    uint32_t idq;
-    float mhq;
-    dn_key(a, q, idq, mhq);
-    const float d = (c.nd.x * ndq.x + c.nd.y * ndq.y) + c.nd.z * ndq.z;
-    bool same = idq == c.id;
-    same &= mhq == c.mh;
-    same &= d >= 0.0f;
-    return same;
 }
 
 // kZ / kL: the depth / luminance term is on (sigma > 0).

@@ -68,9 +68,12 @@ struct mm_ctx {
     // mm_denoise_frames' scratch: the two intermediate images a frame's passes alternate between (one frame
     // each, `dn_img_cap` pixels in all) and the call's packed key records (`dn_keys_cap`).  A call's kernels are
     // ordered after the last call's on the same stream; `dn_done` (recorded after every call) orders them when
-    // the stream changed.
+    // the stream changed.  mm_denoise_frames_var shares all of it, under the same bookkeeping, and keeps the
+    // variance images between its passes beside it (`d_dn_var`: one frame of floats per ping-pong side).
     float4* d_dn_img = nullptr;
     size_t dn_img_cap = 0;
+    float* d_dn_var = nullptr;
+    size_t dn_var_cap = 0;
     uint2* d_dn_keys = nullptr;
     size_t dn_keys_cap = 0;
     hipEvent_t dn_done = nullptr;

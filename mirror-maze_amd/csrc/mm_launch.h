@@ -166,6 +166,21 @@ struct DnPass {
 hipError_t launch_denoise_keys(const float4* al, const uint32_t* id, uint2* keys, size_t n, hipStream_t s);
 hipError_t launch_denoise_pass(const DnPass& pass, hipStream_t s);
 
+// One pass of mm_denoise_frames_var over one frame (denoise_var_kernels.hip); every pointer points at that frame.
+struct DnVarPass {
+    const float4* in = nullptr;      // the pass's input image
+    const float* vin = nullptr;      // the pass's input variance (of the pixel mean's luminance)
+    const float4* nd = nullptr;      // guide: normal_depth
+    const uint2* keys = nullptr;     // guide: the packed (id, bits of albedo.w) records of launch_denoise_keys
+    void* out = nullptr;             // float4 per pixel, or RGBA8 (4 B) when rgba8 is set
+    float* vout = nullptr;           // the pass's output variance; nullptr: not stored
+    uint32_t w = 0, h = 0, tiles_x = 0;  // w * h < 2^31; tiles_x: set by the launcher
+    uint32_t s = 1;                  // tap spacing, 1 << pass
+    float sigma_z = 0.0f, sigma_l = 0.0f, eps_l = 0.0f;  // the stop: sigma_l * sqrt(3x3 mean of vin) + eps_l
+    uint32_t rgba8 = 0;
+};
+hipError_t launch_denoise_var_pass(const DnVarPass& pass, hipStream_t s);
+
 // One frame of mm_accumulate_frames (temporal_kernels.hip); every pointer points at one frame.
 struct TpFrame {
     const float4* color = nullptr;   // the frame as traced

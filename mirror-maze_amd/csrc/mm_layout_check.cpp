@@ -28,6 +28,10 @@ static_assert(sizeof(mm_aov) == 24 && offsetof(mm_aov, albedo) == 8 && offsetof(
 static_assert(sizeof(mm_denoise_params) == 16 && offsetof(mm_denoise_params, sigma_z) == 4 &&
                   offsetof(mm_denoise_params, flags) == 12,
               "mm_denoise_params is four 4-byte fields");
+static_assert(sizeof(mm_denoise_var_params) == 24 && offsetof(mm_denoise_var_params, sigma_z) == 4 &&
+                  offsetof(mm_denoise_var_params, sigma_l) == 8 && offsetof(mm_denoise_var_params, eps_l) == 12 &&
+                  offsetof(mm_denoise_var_params, flags) == 16 && offsetof(mm_denoise_var_params, reserved) == 20,
+              "mm_denoise_var_params is six 4-byte fields");
 static_assert(sizeof(mm_temporal_params) == 16 && offsetof(mm_temporal_params, tol_z) == 4 &&
                   offsetof(mm_temporal_params, w_min) == 8 && offsetof(mm_temporal_params, flags) == 12,
               "mm_temporal_params is four 4-byte fields");

@@ -195,7 +195,7 @@ bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
     return x < y + nb && y < x + na;
 }
 
-// mm_denoise_frames' scratch of at least `n` elements: grown (never shrunk) after everything the device has
+// mm_denoise_frames' and mm_denoise_frames_var's scratch of at least `n` elements: grown (never shrunk) after everything the device has
 // queued is done -- an earlier call's passes may still read the old one, on any stream used so far.
 template <typename T>
 int dn_scratch(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
@@ -355,7 +355,7 @@ void mm_destroy(mm_ctx* c) {
     (void)hipFree(c->d_gather);
     (void)hipFree(c->d_cams);
     if (c->h_cams) (void)hipHostFree(c->h_cams);
-    (void)hipFree(c->d_dn_img); (void)hipFree(c->d_dn_keys);
+    (void)hipFree(c->d_dn_img); (void)hipFree(c->d_dn_keys); (void)hipFree(c->d_dn_var);
     if (c->dn_done) (void)hipEventDestroy(c->dn_done);
     if (c->gather_done) (void)hipEventDestroy(c->gather_done);
     if (c->h_status) (void)hipHostFree(c->h_status);
@@ -755,6 +755,90 @@ int mm_denoise_frames(mm_ctx* c, const float* color_dev, const mm_aov* guides, c
             else a.out = c->d_dn_img + (size_t)(i & 1u) * n_pix;
             HIPC(c, launch_denoise_pass(a, c->stream));
             a.in = reinterpret_cast<const float4*>(a.out);
+        }
+    }
+    HIPC(c, hipEventRecord(c->dn_done, c->stream));
+    return MM_OK;
+}
+
+int mm_denoise_frames_var(mm_ctx* c, const float* color_dev, const mm_aov* guides, const float* vmean_dev,
+                          const mm_denoise_var_params* p, uint32_t n_frames, uint32_t w, uint32_t h, void* out_dev,
+                          float* var_out_dev) {
+    // (argument checks first, and none of them needs the context, as in mm_denoise_frames)
+    if (!p || !guides || !color_dev || !vmean_dev || !out_dev)
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: null argument");
+    if (!guides->normal_depth || !guides->albedo || !guides->id)
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: all three guide buffers are required");
+    if (p->n_passes < 1 || p->n_passes > MM_DENOISE_MAX_PASSES)
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: n_passes must be 1..8");
+    if (p->flags & ~MM_DNV_RGBA8) return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: unknown flags");
+    if (p->reserved != 0) return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: reserved must be 0");
+    if (p->sigma_l > 0.0f && (!(p->eps_l > 0.0f) || !std::isfinite(p->eps_l)))
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: eps_l must be positive and finite when sigma_l > 0");
+    if (w == 0 || h == 0 || n_frames == 0)
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: empty tile or no frames");
+    const bool rgba8 = (p->flags & MM_DNV_RGBA8) != 0;
+    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
+    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
+        misaligned(guides->id, 4) || misaligned(vmean_dev, 4) || misaligned(out_dev, rgba8 ? 4 : 16) ||
+        misaligned(var_out_dev, 4))
+        return fail(c, MM_ERR_INVALID,
+                    "mm_denoise_frames_var: misaligned buffer (float4: 16 bytes; id, variance and RGBA8: 4)");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: more pixels than one call holds");
+    const uint64_t n_all = n_pix * n_frames, out_bytes = n_all * (rgba8 ? 4 : 16);
+    const struct { const void* ptr; uint64_t bytes; } inputs[] = {
+        {color_dev, n_all * 16}, {guides->normal_depth, n_all * 16}, {guides->albedo, n_all * 16},
+        {guides->id, n_all * 4}, {vmean_dev, n_all * 4}};
+    for (const auto& in : inputs)
+        if (ranges_overlap(out_dev, out_bytes, in.ptr, in.bytes) ||
+            (var_out_dev && ranges_overlap(var_out_dev, n_all * 4, in.ptr, in.bytes)))
+            return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: an output overlaps an input");
+    if (var_out_dev && ranges_overlap(var_out_dev, n_all * 4, out_dev, out_bytes))
+        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: the two outputs overlap");
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    const uint32_t n_passes = p->n_passes;
+    // The scratch, its event and its stream bookkeeping are mm_denoise_frames': calls of the two functions take
+    // turns on it in the order they were made.
+    if (n_passes > 1) {
+        const size_t sides = n_passes > 2 ? 2 : 1;
+        if (int rc = dn_scratch(c, c->d_dn_img, c->dn_img_cap, sides * (size_t)n_pix)) return rc;
+        if (int rc = dn_scratch(c, c->d_dn_var, c->dn_var_cap, sides * (size_t)n_pix)) return rc;
+    }
+    if (int rc = dn_scratch(c, c->d_dn_keys, c->dn_keys_cap, (size_t)n_all)) return rc;
+    if (!c->dn_done) HIPC(c, hipEventCreateWithFlags(&c->dn_done, hipEventDisableTiming));
+    if (c->dn_pending && c->dn_stream != c->stream) HIPC(c, hipStreamWaitEvent(c->stream, c->dn_done, 0));
+    const float4* color = reinterpret_cast<const float4*>(color_dev);
+    HIPC(c, launch_denoise_keys(reinterpret_cast<const float4*>(guides->albedo), guides->id, c->d_dn_keys,
+                                (size_t)n_all, c->stream));
+    c->dn_pending = true;
+    c->dn_stream = c->stream;
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const size_t o = (size_t)f * n_pix;
+        DnVarPass a;
+        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
+        a.keys = c->d_dn_keys + o;
+        a.w = w; a.h = h;
+        a.sigma_z = p->sigma_z; a.sigma_l = p->sigma_l; a.eps_l = p->eps_l;
+        a.in = color + o;
+        a.vin = vmean_dev + o;
+        for (uint32_t i = 0; i < n_passes; ++i) {
+            const bool last = i + 1 == n_passes;
+            a.s = 1u << i;
+            a.rgba8 = last && rgba8;
+            if (last) {
+                a.out = rgba8 ? (void*)(reinterpret_cast<uint8_t*>(out_dev) + o * 4)
+                              : (void*)(reinterpret_cast<float4*>(out_dev) + o);
+                a.vout = var_out_dev ? var_out_dev + o : nullptr;
+            } else {
+                a.out = c->d_dn_img + (size_t)(i & 1u) * n_pix;
+                a.vout = c->d_dn_var + (size_t)(i & 1u) * n_pix;
+            }
+            HIPC(c, launch_denoise_var_pass(a, c->stream));
+            a.in = reinterpret_cast<const float4*>(a.out);
+            a.vin = a.vout;
         }
     }
     HIPC(c, hipEventRecord(c->dn_done, c->stream));

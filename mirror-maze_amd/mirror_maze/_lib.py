@@ -50,7 +50,7 @@ MM_OWN_STREAM = C.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF).value  # (void*)-1
 MM_COMM_ID_BYTES, MM_GATHER_SELF_VIA_RCCL = 128, 1
 MM_AOV_ID_MISS, MM_AOV_ID_FAILED, MM_AOV_ID_RECT = 0xFFFFFFFF, 0xFFFFFFFE, 0x00FFFFFF
 MM_AOV_ID_SURFACE, MM_AOV_ID_MIRROR_END = 0x40000000, 0x80000000
-MM_DENOISE_MAX_PASSES, MM_DN_RGBA8 = 8, 1
+MM_DENOISE_MAX_PASSES, MM_DN_RGBA8, MM_DNV_RGBA8 = 8, 1, 1
 
 
 class mm_rect(C.Structure):
@@ -87,6 +87,11 @@ class mm_aov(C.Structure):
 
 class mm_denoise_params(C.Structure):
     _fields_ = [("n_passes", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("flags", C.c_uint32)]
+
+
+class mm_denoise_var_params(C.Structure):
+    _fields_ = [("n_passes", C.c_uint32), ("sigma_z", C.c_float), ("sigma_l", C.c_float), ("eps_l", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class mm_temporal_params(C.Structure):
@@ -140,6 +145,8 @@ EXPORTS = {
                                C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mm_aov)]),
     "mm_denoise_frames": (C.c_int, [P, P, C.POINTER(mm_aov), C.POINTER(mm_denoise_params), C.c_uint32, C.c_uint32,
                                     C.c_uint32, P]),
+    "mm_denoise_frames_var": (C.c_int, [P, P, C.POINTER(mm_aov), P, C.POINTER(mm_denoise_var_params), C.c_uint32,
+                                        C.c_uint32, C.c_uint32, P, P]),
     "mm_accumulate_frames": (C.c_int, [P, C.POINTER(mm_uniform), P, P, C.POINTER(mm_aov), C.POINTER(mm_temporal_prev),
                                        C.POINTER(mm_temporal_params), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, P]),

@@ -348,6 +348,62 @@ class Renderer:
                                             out.data_ptr()))
         return out
 
+    def denoise_var(self, color, aov, var, count, n_passes: int = 4, sigma_z: float = 0.02, sigma_l: float = 8.0,
+                    eps_l: float = 1e-2, rgba8: bool = False, out=None, var_out=None, return_var: bool = False):
+        """Variance-guided a-trous denoise (mm_denoise_frames_var): denoise()
+        with the luminance stop of every pixel at sigma_l standard deviations
+        of the pixel mean (from a 3x3 of the variance around it) plus eps_l,
+        not halved per pass.  `color`, `aov`, `rgba8`, `out`: as in denoise().
+        `var`: an (h, w) or (n, h, w) float32 CUDA tensor, the variance of ONE
+        sample's luminance, what trace_tile_var returns or refine() keeps;
+        `count`: the samples each pixel holds, a number or a tensor of var's
+        shape.  The filter takes var / count, formed here.  Returns `out`, or
+        with return_var or a `var_out` tensor (float32, var's shape) the pair
+        (out, var_out): the variance of the filtered mean's luminance, the taps
+        taken as independent.  The defaults are from the sweep in
+        profiles/denoise_var/quality.txt.  The inputs are not written.  (var / count is a
+        torch operation on torch's current stream: with a pinned stream, call
+        this under that stream, as refine().)"""
+        import torch
+
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+                and color.dim() in (3, 4) and color.shape[-1] == 4):
+            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
+        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        lead = tuple(color.shape[:-1])
+        a = self._aov_frames(aov, n, h, w, color.device, "aov")
+        if not (torch.is_tensor(var) and var.is_cuda and var.device == color.device and var.dtype == torch.float32
+                and tuple(var.shape) in (lead, (n, h, w) if n == 1 else lead, (h, w) if n == 1 else lead)):
+            raise ValueError(f"var must be a float32 tensor of shape {lead} on {color.device}")
+        if torch.is_tensor(count):
+            if not (count.device == color.device and tuple(count.shape) == tuple(var.shape)):
+                raise ValueError("count must be a number or a tensor of var's shape on its device")
+        elif not float(count) > 0:
+            raise ValueError("count must be positive")
+        if not 1 <= int(n_passes) <= _lib.MM_DENOISE_MAX_PASSES:
+            raise ValueError(f"n_passes must be 1..{_lib.MM_DENOISE_MAX_PASSES}")
+        if out is None:
+            out = torch.empty(color.shape, dtype=torch.uint8 if rgba8 else torch.float32, device=color.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
+                  and out.dtype in (torch.float32, torch.uint8) and out.shape == color.shape
+                  and not (rgba8 and out.dtype != torch.uint8)):
+            raise ValueError("out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
+        if var_out is None:
+            var_out = torch.empty(var.shape, dtype=torch.float32, device=color.device) if return_var else None
+        elif not (torch.is_tensor(var_out) and var_out.is_cuda and var_out.device == color.device
+                  and var_out.is_contiguous() and var_out.dtype == torch.float32 and var_out.shape == var.shape):
+            raise ValueError("var_out must be a contiguous float32 CUDA tensor of var's shape")
+        r8 = out.dtype == torch.uint8
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        vmean = (var / count).to(torch.float32).contiguous()  # bookkeeping, as merge_samples is
+        p = _lib.mm_denoise_var_params(int(n_passes), float(sigma_z), float(sigma_l), float(eps_l),
+                                       _lib.MM_DNV_RGBA8 if r8 else 0, 0)
+        self._check(lib().mm_denoise_frames_var(self._ctx, color.data_ptr(), C.byref(a), vmean.data_ptr(),
+                                                C.byref(p), n, w, h, out.data_ptr(),
+                                                None if var_out is None else var_out.data_ptr()))
+        return out if var_out is None else (out, var_out)
+
     def _aov_frames(self, aov, n, h, w, device, what):
         """The mm_aov of an aov dict whose buffers hold n frames of h x w on `device`."""
         import torch

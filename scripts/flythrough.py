@@ -11,6 +11,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 10 --frames 30 --no-render     # the camera path only: no GPU
     python scripts/flythrough.py --maze 32 --frames 40 --aov aov/       # + feature buffers per frame
     python scripts/flythrough.py --maze 32 --frames 40 --denoise        # + frame_NNNN_dn.png beside each frame
+    python scripts/flythrough.py --maze 32 --frames 40 --denoise-var    # + frame_NNNN_dnv.png: the variance-guided filter
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate     # + frame_NNNN_acc.png beside each frame
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate --top-up 2:24   # + extra samples where the history is short
 
@@ -50,6 +51,13 @@ variance); the share of pixels each round took is printed per frame.  With
 --denoise the denoiser runs on the refined frames.  Not with --accumulate: a
 history of frames with unequal sample counts is not what mm_accumulate_frames
 averages.
+
+--denoise-var also writes frame_NNNN_dnv.png beside each frame: the frame through
+Renderer.denoise_var (mm_denoise_frames_var, its defaults), whose luminance stop
+follows each pixel's own noise.  The frames are then traced one by one through
+Renderer.trace_tile_var, as with --refine, and with --refine the filter runs on
+the refined frames with the variance and the sample counts the rounds left.  Not
+with --accumulate: mm_accumulate_frames carries no variance through the history.
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -92,6 +100,9 @@ def main(argv=None) -> int:
                     help="also write per-frame feature buffers: DIR/frame_NNNN/{normal.png,depth.npy,id.npy}")
     ap.add_argument("--denoise", action="store_true",
                     help="also write frame_NNNN_dn.png: the frame through Renderer.denoise, guided by its feature buffers")
+    ap.add_argument("--denoise-var", action="store_true",
+                    help="also write frame_NNNN_dnv.png: the frame through Renderer.denoise_var, its luminance stop "
+                         "scaled by each pixel's sample variance (composes with --refine, not with --accumulate)")
     ap.add_argument("--accumulate", action="store_true",
                     help="also write frame_NNNN_acc.png: the frame through Renderer.accumulate (temporal accumulation); "
                          "with --denoise the denoiser runs on the accumulated frames")
@@ -105,6 +116,10 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
         ap.error("--frames and --batch must be positive")
+    if a.denoise_var and a.accumulate:
+        ap.error("--denoise-var does not go with --accumulate: no variance is carried through the accumulated history")
+    if a.denoise_var and a.spp < 2:
+        ap.error("--denoise-var needs --spp of at least 2 (a sample variance)")
     top_up = None  # (n_min, extra spp)
     if a.top_up is not None:
         if not a.accumulate:
@@ -151,17 +166,19 @@ def main(argv=None) -> int:
     out_dir = Path(a.out)
     out_dir.mkdir(parents=True, exist_ok=True)
     u = player.uniform()  # view size and chunk width; its camera is not used
-    floats = a.denoise or a.accumulate or refine is not None  # the batch is traced as float frames
+    with_var = refine is not None or a.denoise_var  # the frames are traced with their per-pixel sample variance
+    floats = a.denoise or a.accumulate or with_var  # the batch is traced as float frames
     prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera
     with Renderer(0) as r:
         r.upload_scene(scene)
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
-            if refine:
+            if with_var:
                 # frame by frame (a single-frame variance call runs at any size; frame k is the batch launch's)
                 img = torch.empty((len(batch), a.height, a.width, 4), dtype=torch.float32, device="cuda:0")
                 var = torch.empty((len(batch), a.height, a.width), dtype=torch.float32, device="cuda:0")
+                count = torch.full_like(var, float(a.spp))  # the samples each pixel holds
                 us = []
                 for k in range(len(batch)):
                     uk = mm_uniform.from_buffer_copy(u)
@@ -175,14 +192,13 @@ def main(argv=None) -> int:
             r.sync()
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
-            print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if refine else 'one launch'}, "
+            print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if with_var else 'one launch'}, "
                   f"{out_dir}/frame_{f0:04d}.png ...", flush=True)
             if refine:
                 for k in range(len(batch)):
-                    count = torch.full((a.height, a.width), float(a.spp), dtype=torch.float32, device="cuda:0")
                     shares = []
                     for rnd in range(refine[2]):
-                        n_sel = r.refine(us[k], e, img[k], var[k], count, refine[0], refine[1],
+                        n_sel = r.refine(us[k], e, img[k], var[k], count[k], refine[0], refine[1],
                                          2**20 + 64 * (f0 + k) + rnd)
                         shares.append(f"{100.0 * n_sel / (a.width * a.height):.2f} %")
                         if n_sel == 0:
@@ -193,7 +209,7 @@ def main(argv=None) -> int:
                 r.sync()
                 for k in range(len(batch)):
                     write_png(out_dir / f"frame_{f0 + k:04d}_ref.png", done[k])
-            if a.aov is None and not (a.denoise or a.accumulate):
+            if a.aov is None and not (a.denoise or a.denoise_var or a.accumulate):
                 continue
             bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
                                want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
@@ -223,6 +239,13 @@ def main(argv=None) -> int:
                 for k in range(len(batch)):
                     write_png(out_dir / f"frame_{f0 + k:04d}_dn.png", clean[k])
                 print(f"# frames {f0}..{f0 + len(batch) - 1}: denoised, {out_dir}/frame_{f0:04d}_dn.png ...", flush=True)
+            if a.denoise_var:
+                clean = r.denoise_var(img, bufs, var, count, rgba8=True).cpu().numpy()
+                r.sync()
+                for k in range(len(batch)):
+                    write_png(out_dir / f"frame_{f0 + k:04d}_dnv.png", clean[k])
+                print(f"# frames {f0}..{f0 + len(batch) - 1}: variance-guided denoise, "
+                      f"{out_dir}/frame_{f0:04d}_dnv.png ...", flush=True)
             r.sync()
             if a.aov is None:
                 continue
