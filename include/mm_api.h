@@ -499,6 +499,81 @@ int  mm_trace_pixels_var(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
                          const uint32_t* pixels_dev, uint64_t n_pixels,
                          void* out_dev, float* var_dev, mm_stats* stats);
 
+/* ---- variance through the history ----------------------------------------------
+ * mm_accumulate_frames with the variance of the pixel mean carried beside the
+ * colour, and a weight per pixel and frame: the accumulated frame then has
+ * what mm_denoise_frames_var (vmean = var_out) and a noise-driven top-up ask
+ * for, and frames with unequal sample counts (Renderer.refine) accumulate.
+ *
+ * Everything mm_accumulate_frames states holds: uni, cams, color_dev, guides,
+ * p, the window, the projection, the four taps, the key test, w_min, IEEE
+ * binary32 in the order written with no contraction, subnormals kept, / and
+ * sqrtf correctly rounded.  vmean_dev: n_frames*w*h floats (4-byte aligned),
+ * the variance of the frame's pixel-MEAN luminance (mm_trace_tile_var's var /
+ * the pixel's sample count).  weight_dev: n_frames*w*h floats or NULL, the
+ * frame's weight m per pixel in frames (samples held / frame spp, e.g. after
+ * Renderer.refine); NULL: 1 everywhere.  prev: as mm_temporal_prev, and var,
+ * that frame's var_out of the earlier call.  out_dev: n_frames*w*h float4,
+ * out.a is the history length N in frames (a float >= the least weight);
+ * var_out_dev: n_frames*w*h floats, the variance of out's luminance.  The
+ * call is defined for finite m > 0 and finite V >= 0.  Frame f reads frame
+ * f-1's colour AND variance from this call's own outputs; for f = 0 it reads
+ * prev, or none if prev is NULL.  V' is the history frame's variance output.
+ * For pixel p of frame f:
+ *   m  = weight ? weight[f][p] : 1.0f;  Vc = vmean[f][p]
+ *   NOHIST: out = (C.r, C.g, C.b, m);  Vout = Vc
+ *   SV = 0; in the tap loop, for every tap that is not skipped, after W = W + g:
+ *     SV = SV + (g * g) * V'_q
+ *   unless W >= w_min: NOHIST
+ *   Hc = S / W;  VH = SV / (W * W)
+ *   N  = fminf(SN / W + m, fmaxf((float)n_max, m))          (m / N never exceeds 1)
+ *   out.c = Hc.c + ((C.c - Hc.c) * m) / N  (c = r, g, b);  out.a = N
+ *   b = m / N;  c = 1.0f - b
+ *   Vout = (c * c) * VH + (b * b) * Vc
+ * With weight_dev == NULL out_dev equals mm_accumulate_frames' output for the
+ * same arguments on all bits: (C - Hc) * 1.0f is exact, fmaxf(n_max, 1) is
+ * n_max, and NOHIST writes alpha 1.0f.
+ *
+ * VH weights the taps' variances by g*g, the form mm_denoise_frames_var uses:
+ * it takes the taps as independent.  Neighbouring history pixels share
+ * ancestors once a frame has been reprojected between pixel centres, so Vout
+ * falls short of the true variance of out (a desk model of iid noise under
+ * repeated bilinear reprojection, scripts/temporal_var_model.py: 0.78..1.00 of
+ * it over 8 frames; the linear form sum g V' / W gives 1.0..4.7); DESIGN.md s4
+ * "Variance through the history" has what was measured on rendered frames.
+ *
+ * MM_ERR_INVALID: everything mm_accumulate_frames rejects; a null vmean_dev or
+ * var_out_dev; prev with a null var; a vmean_dev, weight_dev, var_out_dev or
+ * prev->var that is not 4-byte aligned; out_dev or var_out_dev overlapping any
+ * input, a prev buffer, or each other.  None of the checks needs the context;
+ * a null context is refused last.  Enqueued on the context's stream, one
+ * launch per frame in stream order; the inputs are never written; the call
+ * keeps no scratch and needs no uploaded scene. */
+int  mm_accumulate_frames_var(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams,
+                              const float* color_dev, const mm_aov* guides,
+                              const float* vmean_dev, const float* weight_dev,
+                              const mm_temporal_prev_var* prev, const mm_temporal_params* p,
+                              uint32_t n_frames, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                              void* out_dev, float* var_out_dev);
+
+/* mm_blend_pixels with the variance image beside the colour, both in place.
+ * image_dev, the window, pixels_dev, extra_dev, n_pixels, m: as mm_blend_pixels.
+ * var_dev: w*h floats (4-byte aligned), the window's var_out of
+ * mm_accumulate_frames_var; extra_vmean_dev: n_pixels floats (4-byte aligned),
+ * the variance of the extra samples' MEAN (mm_trace_pixels_var's var / extra
+ * spp).  The colour and alpha are exactly mm_blend_pixels'; in addition, for an
+ * entry that is not skipped, with Nn = A.a + m as there:
+ *   b = m / Nn;  c = 1.0f - b
+ *   var[p] = (c * c) * var[p] + (b * b) * extra_vmean[e]
+ * The skip rule, the duplicate rule and n_pixels = 0 are mm_blend_pixels'.
+ * MM_ERR_INVALID: everything mm_blend_pixels rejects; a null or misaligned
+ * var_dev or extra_vmean_dev; var_dev overlapping image_dev, the list,
+ * extra_dev or extra_vmean_dev; the list or extra_vmean_dev overlapping
+ * image_dev. */
+int  mm_blend_pixels_var(mm_ctx* ctx, float* image_dev, float* var_dev,
+                         uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const uint32_t* pixels_dev,
+                         const float* extra_dev, const float* extra_vmean_dev, uint64_t n_pixels, float m);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */

@@ -136,6 +136,13 @@ typedef struct mm_temporal_prev {     /* the frame before frame 0, from an earli
     mm_camera    cam;     /* that frame's camera */
 } mm_temporal_prev;
 
+typedef struct mm_temporal_prev_var { /* 80 bytes: mm_temporal_prev for mm_accumulate_frames_var */
+    const float* color;   /* DEVICE, w*h float4: an earlier call's out frame (alpha = N) */
+    mm_aov       guides;  /* DEVICE, that frame's three buffers (one frame), all required */
+    mm_camera    cam;     /* that frame's camera */
+    const float* var;     /* DEVICE, w*h floats: that frame's var_out of the earlier call */
+} mm_temporal_prev_var;
+
 /* Return codes (0 = success; never panics or throws across the ABI). */
 #define MM_OK               0
 #define MM_ERR_INVALID     -1  /* bad argument / shape                        */

@@ -211,6 +211,24 @@ struct TpBlend {
 };
 hipError_t launch_blend_pixels(const TpBlend& blend, hipStream_t s);
 
+// One frame of mm_accumulate_frames_var (temporal_var_kernels.hip): TpFrame, and the variances beside it.
+struct TpFrameVar {
+    TpFrame f;                       // as for mm_accumulate_frames
+    const float* vmean = nullptr;    // the frame's variance of the pixel mean's luminance
+    const float* weight = nullptr;   // the frame's weight per pixel, in frames; nullptr: 1 everywhere (own kernel)
+    const float* h_var = nullptr;    // the history frame's variance output; set whenever f.h_color is
+    float* vout = nullptr;
+};
+hipError_t launch_temporal_frame_var(const TpFrameVar& frame, hipStream_t s);
+
+// mm_blend_pixels_var (temporal_var_kernels.hip): TpBlend, and the variance image beside it.
+struct TpBlendVar {
+    TpBlend b;                          // as for mm_blend_pixels
+    float* var = nullptr;               // the window's w * h variances, updated in place
+    const float* extra_vmean = nullptr; // n entries: the variance of the extra samples' mean
+};
+hipError_t launch_blend_pixels_var(const TpBlendVar& blend, hipStream_t s);
+
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);
 // The same pixel, and the unbiased sample variance of the samples' luminance into var[pixel] (spp >= 2;

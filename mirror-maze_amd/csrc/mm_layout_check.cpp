@@ -38,5 +38,8 @@ static_assert(sizeof(mm_temporal_params) == 16 && offsetof(mm_temporal_params, t
 static_assert(sizeof(mm_temporal_prev) == 72 && offsetof(mm_temporal_prev, guides) == 8 &&
                   offsetof(mm_temporal_prev, cam) == 32,
               "mm_temporal_prev is a pointer, an mm_aov and an mm_camera");
+static_assert(sizeof(mm_temporal_prev_var) == 80 && offsetof(mm_temporal_prev_var, guides) == 8 &&
+                  offsetof(mm_temporal_prev_var, cam) == 32 && offsetof(mm_temporal_prev_var, var) == 72,
+              "mm_temporal_prev_var is mm_temporal_prev and a pointer");
 
 extern "C" int mm_layout_ok(void) { return 1; }

@@ -915,6 +915,94 @@ int mm_accumulate_frames(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, 
     return MM_OK;
 }
 
+int mm_accumulate_frames_var(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const float* color_dev,
+                             const mm_aov* guides, const float* vmean_dev, const float* weight_dev,
+                             const mm_temporal_prev_var* prev, const mm_temporal_params* p, uint32_t n_frames,
+                             uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out_dev, float* var_out_dev) {
+    // (argument checks first, and none of them needs the context, as in mm_accumulate_frames)
+    if (!u || !cams || !color_dev || !guides || !vmean_dev || !p || !out_dev || !var_out_dev)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: null argument");
+    if (!guides->normal_depth || !guides->albedo || !guides->id)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: all three guide buffers are required");
+    if (prev && (!prev->color || !prev->guides.normal_depth || !prev->guides.albedo || !prev->guides.id || !prev->var))
+        return fail(c, MM_ERR_INVALID,
+                    "mm_accumulate_frames_var: prev needs its colour, all three guide buffers and its variance");
+    if (p->n_max < 1 || p->n_max > 65535)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: n_max must be 1..65535");
+    if (!(p->tol_z > 0.0f) || !std::isfinite(p->tol_z))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: tol_z must be positive and finite");
+    if (!(p->w_min > 0.0f && p->w_min <= 1.0f))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: w_min must be in (0, 1]");
+    if (p->flags) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: unknown flags");
+    if (w == 0 || h == 0 || n_frames == 0)
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: empty tile or no frames");
+    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
+    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
+        misaligned(guides->id, 4) || misaligned(out_dev, 16) || misaligned(vmean_dev, 4) ||
+        misaligned(weight_dev, 4) || misaligned(var_out_dev, 4) ||
+        (prev && (misaligned(prev->color, 16) || misaligned(prev->guides.normal_depth, 16) ||
+                  misaligned(prev->guides.albedo, 16) || misaligned(prev->guides.id, 4) || misaligned(prev->var, 4))))
+        return fail(c, MM_ERR_INVALID,
+                    "mm_accumulate_frames_var: misaligned buffer (float4: 16 bytes, id and variances: 4)");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: more pixels than one call holds");
+    if ((uint64_t)x0 + w > (1ull << 24) || (uint64_t)y0 + h > (1ull << 24))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: the window ends beyond pixel 2^24");
+    const uint64_t n_all = n_pix * n_frames;
+    // either output against every input and every prev buffer, and the two outputs against each other
+    auto hits_input = [&](const void* o, uint64_t bytes) {
+        return ranges_overlap(o, bytes, color_dev, n_all * 16) ||
+               ranges_overlap(o, bytes, guides->normal_depth, n_all * 16) ||
+               ranges_overlap(o, bytes, guides->albedo, n_all * 16) || ranges_overlap(o, bytes, guides->id, n_all * 4) ||
+               ranges_overlap(o, bytes, vmean_dev, n_all * 4) ||
+               (weight_dev && ranges_overlap(o, bytes, weight_dev, n_all * 4)) ||
+               (prev && (ranges_overlap(o, bytes, prev->color, n_pix * 16) ||
+                         ranges_overlap(o, bytes, prev->guides.normal_depth, n_pix * 16) ||
+                         ranges_overlap(o, bytes, prev->guides.albedo, n_pix * 16) ||
+                         ranges_overlap(o, bytes, prev->guides.id, n_pix * 4) ||
+                         ranges_overlap(o, bytes, prev->var, n_pix * 4)));
+    };
+    if (hits_input(out_dev, n_all * 16) || hits_input(var_out_dev, n_all * 4))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: an output overlaps an input");
+    if (ranges_overlap(out_dev, n_all * 16, var_out_dev, n_all * 4))
+        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: the two outputs overlap");
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    // One launch per frame, in stream order, as mm_accumulate_frames: frame f reads frame f - 1's colour and
+    // variance outputs, which the kernel boundary makes visible; no scratch.
+    TpFrameVar b;
+    TpFrame& a = b.f;
+    a.view_w = u->view_w; a.view_h = u->view_h;
+    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
+    a.n_max = (float)p->n_max; a.tol_z = p->tol_z; a.w_min = p->w_min;
+    if (prev) {
+        a.h_color = reinterpret_cast<const float4*>(prev->color);
+        a.h_nd = reinterpret_cast<const float4*>(prev->guides.normal_depth);
+        a.h_al = reinterpret_cast<const float4*>(prev->guides.albedo);
+        a.h_id = prev->guides.id;
+        a.h_cam = prev->cam;
+        b.h_var = prev->var;
+    }
+    for (uint32_t f = 0; f < n_frames; ++f) {
+        const size_t o = (size_t)f * n_pix;
+        a.color = reinterpret_cast<const float4*>(color_dev) + o;
+        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
+        a.al = reinterpret_cast<const float4*>(guides->albedo) + o;
+        a.id = guides->id + o;
+        a.out = reinterpret_cast<float4*>(out_dev) + o;
+        a.cam = cams[f];
+        b.vmean = vmean_dev + o;
+        b.weight = weight_dev ? weight_dev + o : nullptr;
+        b.vout = var_out_dev + o;
+        HIPC(c, launch_temporal_frame_var(b, c->stream));
+        a.h_color = a.out; a.h_nd = a.nd; a.h_al = a.al; a.h_id = a.id;
+        a.h_cam = a.cam;
+        b.h_var = b.vout;
+    }
+    return MM_OK;
+}
+
 int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
     if (!c) return MM_ERR_INVALID;
     if (!c->d_fb) return fail(c, MM_ERR_INVALID, "mm_read_framebuffer: nothing rendered yet");
@@ -1273,6 +1361,52 @@ int mm_blend_pixels(mm_ctx* c, float* image_dev, uint32_t x0, uint32_t y0, uint3
     b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
     b.m = m;
     HIPC(c, launch_blend_pixels(b, c->stream));
+    return MM_OK;
+}
+
+int mm_blend_pixels_var(mm_ctx* c, float* image_dev, float* var_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                        const uint32_t* pixels_dev, const float* extra_dev, const float* extra_vmean_dev,
+                        uint64_t n_pixels, float m) {
+    // (argument checks first, and none of them needs the context, as in mm_blend_pixels)
+    if (!image_dev || !var_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: null image or variance");
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7FFFFFFFull)
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: empty window or more than 2^31 - 1 pixels");
+    if (!(m > 0.0f) || !std::isfinite(m))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: m must be positive and finite");
+    if (reinterpret_cast<uintptr_t>(image_dev) % 16 || reinterpret_cast<uintptr_t>(var_dev) % 4)
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: misaligned image or variance");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (ranges_overlap(image_dev, n_pix * 16, var_dev, n_pix * 4))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: var_dev overlaps the image");
+    if (n_pixels == 0) return c ? MM_OK : MM_ERR_INVALID;
+    if (!pixels_dev || !extra_dev || !extra_vmean_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: null argument");
+    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(extra_dev) % 16 ||
+        reinterpret_cast<uintptr_t>(extra_vmean_dev) % 4)
+        return fail(c, MM_ERR_INVALID,
+                    "mm_blend_pixels_var: misaligned buffer (float4: 16 bytes, the list: 8, variances: 4)");
+    if (n_pixels > (1ull << 38))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: more entries than one launch holds");
+    if (ranges_overlap(image_dev, n_pix * 16, extra_dev, n_pixels * 16) ||
+        ranges_overlap(image_dev, n_pix * 16, extra_vmean_dev, n_pixels * 4) ||
+        ranges_overlap(image_dev, n_pix * 16, pixels_dev, n_pixels * 8))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: an input overlaps the image");
+    if (ranges_overlap(var_dev, n_pix * 4, extra_dev, n_pixels * 16) ||
+        ranges_overlap(var_dev, n_pix * 4, extra_vmean_dev, n_pixels * 4) ||
+        ranges_overlap(var_dev, n_pix * 4, pixels_dev, n_pixels * 8))
+        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: an input overlaps var_dev");
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    TpBlendVar v;
+    TpBlend& b = v.b;
+    b.image = reinterpret_cast<float4*>(image_dev);
+    b.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+    b.extra = reinterpret_cast<const float4*>(extra_dev);
+    b.n = n_pixels;
+    b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
+    b.m = m;
+    v.var = var_dev;
+    v.extra_vmean = extra_vmean_dev;
+    HIPC(c, launch_blend_pixels_var(v, c->stream));
     return MM_OK;
 }
 

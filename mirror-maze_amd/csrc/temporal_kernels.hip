@@ -13,6 +13,9 @@
 //                     slower than taps that fall exactly on their own pixels
 //                     (profiles/temporal/ab.txt).
 //
+// The rotation, the projection, a tap's address and the key test are mm_temporal.h's, shared with
+// k_temporal_frame_var (temporal_var_kernels.hip), which runs the same reprojection.
+//
 // Frame f reads what frame f - 1's launch wrote, so a call is one launch per
 // frame in stream order: the kernel boundary is what makes frame f - 1's
 // stores visible, and no thread reads a pixel of its own launch's output.
@@ -29,42 +32,20 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_launch.h"
+#include "mm_temporal.h"
 #include "mm_trace.h"
 
 namespace mm {
 
 namespace {
 
-// The rotation primary_dir applies to its normalised direction (mm_device.h), with the quaternion as arguments.
-__device__ __forceinline__ F3 tp_rot(F3 q, float qw, F3 v) {
-    const F3 nq = F3{-q.x, -q.y, -q.z};
-    const float s1 = -dot3(nq, v);
-    const F3 c1 = F3{nq.y * v.z - nq.z * v.y, nq.z * v.x - nq.x * v.z, nq.x * v.y - nq.y * v.x};
-    const F3 v1 = c1 + qw * v;
-    const F3 c2 = F3{v1.y * q.z - v1.z * q.y, v1.z * q.x - v1.x * q.z, v1.x * q.y - v1.y * q.x};
-    return (qw * v1 + s1 * q) + c2;
-}
-
 // The history of pixel (i, j), whose colour is C and id idp: false for NOHIST (o is then untouched).
 __device__ __forceinline__ bool tp_history(const TpFrame& a, uint32_t i, uint32_t j, uint32_t p, const float4& C,
                                            uint32_t idp, float4& o) {
     const float4 ndp = a.nd[p];
     const float mhp = a.al[p].w;
-    mm_uniform u;
-    u.cam = a.cam;
-    u.view_w = a.view_w;
-    u.view_h = a.view_h;
-    const F3 d = primary_dir(u, a.x0 + i, a.y0 + j);
-    const F3 X = F3{a.cam.center[0], a.cam.center[1], a.cam.center[2]} + ndp.w * d;
-    const F3 r = X - F3{a.h_cam.center[0], a.h_cam.center[1], a.h_cam.center[2]};
-    const F3 l = tp_rot(F3{-a.h_cam.quat[0], -a.h_cam.quat[1], -a.h_cam.quat[2]}, a.h_cam.quat[3], r);
-    const float dp = sqrtf(dot3(r, r));
-    if (!(l.z > 0.0f)) return false;
-    const float vx = a.h_cam.viewport[0], vy = a.h_cam.viewport[1];
-    const float sx = ((((l.x * a.h_cam.focal) / l.z) + vx * 0.5f) * a.view_w) / vx;
-    const float sy = ((((l.y * a.h_cam.focal) / l.z) + vy * 0.5f) * a.view_h) / vy;
-    const float uu = sx - (float)a.x0, vv = sy - (float)a.y0;
-    if (!(uu >= -1.0f && uu < (float)a.w && vv >= -1.0f && vv < (float)a.h)) return false;
+    float uu, vv, dp;
+    if (!tp_project(a, i, j, ndp.w, uu, vv, dp)) return false;
     // (uu in [-1, w), vv in [-1, h), w and h at most 2^24: the conversions are exact and i0 + 1 <= w, j0 + 1 <= h)
     const float fu = floorf(uu), fv = floorf(vv);
     const float fa = uu - fu, fb = vv - fv;
@@ -73,21 +54,13 @@ __device__ __forceinline__ bool tp_history(const TpFrame& a, uint32_t i, uint32_
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int dx = t & 1, dy = t >> 1;
-        const int qx = i0 + dx, qy = j0 + dy;
-        const bool in = (uint32_t)qx < a.w && (uint32_t)qy < a.h;
-        // clamped: always a pixel of the history frame (cy * w + cx < w * h < 2^31)
-        const uint32_t cx = (uint32_t)min(max(qx, 0), (int)a.w - 1), cy = (uint32_t)min(max(qy, 0), (int)a.h - 1);
-        const uint32_t q = cy * a.w + cx;
+        bool in;
+        const uint32_t q = tp_tap(a, i0 + dx, j0 + dy, in);
         const float4 Hq = a.h_color[q];
         const float4 ndq = a.h_nd[q];
         const float mhq = a.h_al[q].w;
         const uint32_t idq = a.h_id[q];
-        const float dn = (ndp.x * ndq.x + ndp.y * ndq.y) + ndp.z * ndq.z;
-        bool take = in;
-        take &= idq == idp;
-        take &= mhq == mhp;
-        take &= dn >= 0.0f;
-        take &= fabsf(dp - ndq.w) <= a.tol_z * (dp + ndq.w);
+        const bool take = tp_key(a, in, idq, idp, mhq, mhp, ndp, ndq, dp);
         const float g = (dx ? fa : 1.0f - fa) * (dy ? fb : 1.0f - fb);
         const float nx = Sx + g * Hq.x, ny = Sy + g * Hq.y, nz = Sz + g * Hq.z, nn = SN + g * Hq.w, nw = W + g;
         Sx = take ? nx : Sx;

@@ -102,6 +102,10 @@ class mm_temporal_prev(C.Structure):
     _fields_ = [("color", C.c_void_p), ("guides", mm_aov), ("cam", mm_camera)]
 
 
+class mm_temporal_prev_var(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("guides", mm_aov), ("cam", mm_camera), ("var", C.c_void_p)]
+
+
 class mm_rng(C.Structure):
     _fields_ = [("key", C.c_uint32 * 8), ("counter", C.c_uint64), ("buf", C.c_uint32 * 64), ("pos", C.c_uint32)]
 
@@ -154,6 +158,11 @@ EXPORTS = {
                                   C.POINTER(mm_stats)]),
     "mm_blend_pixels": (C.c_int, [P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, C.c_uint64,
                                   C.c_float]),
+    "mm_accumulate_frames_var": (C.c_int, [P, C.POINTER(mm_uniform), P, P, C.POINTER(mm_aov), P, P,
+                                           C.POINTER(mm_temporal_prev_var), C.POINTER(mm_temporal_params), C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P]),
+    "mm_blend_pixels_var": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, C.c_uint64,
+                                      C.c_float]),
     "mm_trace_tile_var": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, C.POINTER(mm_stats)]),
     "mm_trace_pixels_var": (C.c_int, [P, C.POINTER(mm_uniform), C.POINTER(mm_ext), P, C.c_uint64, P, P,

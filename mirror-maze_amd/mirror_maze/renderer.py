@@ -469,6 +469,77 @@ class Renderer:
                                                w, h, out.data_ptr()))
         return out
 
+    def accumulate_var(self, uniform: _lib.mm_uniform, cameras, color, aov, vmean, weight=None, prev=None,
+                       n_max: int = 32, tol_z: float = 0.02, w_min: float = 0.25, x0: int = 0, y0: int = 0, out=None,
+                       var_out=None):
+        """accumulate() with the variance of the pixel mean carried through the
+        history (mm_accumulate_frames_var).  `color`, `cameras`, `aov`, the
+        parameters and the window: as in accumulate().  `vmean`: a float32 CUDA
+        tensor of color's shape without the last axis, the variance of each
+        frame's pixel-MEAN luminance (trace_tile_var's var / the samples the
+        pixel holds).  `weight`: None, or a tensor of vmean's shape, the frame's
+        weight per pixel in frames (samples held / frame spp, e.g. count /
+        ext.spp after refine()); None is 1 everywhere, and the colours are then
+        accumulate()'s bit for bit.  `prev` is a (color, aov, camera, var)
+        quadruple: an earlier call's last output frame, that frame's guides, its
+        camera and its var_out.  Returns (out, var_out): the accumulated frames
+        (alpha = history length in frames) and the variance of their luminance,
+        the taps taken as independent; var_out feeds denoise_var() with count 1
+        and select_noisy() with count 1.  The inputs are not written."""
+        import torch
+
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+                and color.dim() in (3, 4) and color.shape[-1] == 4):
+            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
+        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        lead = tuple(color.shape[:-1])
+        cams = self._cameras(cameras)
+        if cams.shape[0] != n:
+            raise ValueError(f"{n} frames need {n} cameras, not {cams.shape[0]}")
+        a = self._aov_frames(aov, n, h, w, color.device, "aov")
+        if not 1 <= int(n_max) <= 65535:
+            raise ValueError("n_max must be 1..65535")
+
+        def plane(t, what, shape=lead):
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
+                    and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{what} must be a contiguous float32 tensor of shape {shape} on {color.device}")
+            return t
+
+        plane(vmean, "vmean")
+        if weight is not None:
+            plane(weight, "weight")
+        if out is None:
+            out = torch.empty_like(color)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
+                  and out.dtype == torch.float32 and out.shape == color.shape):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of color's shape")
+        if var_out is None:
+            var_out = torch.empty(lead, dtype=torch.float32, device=color.device)
+        else:
+            plane(var_out, "var_out")
+        pv = None
+        if prev is not None:
+            pc, pa, pcam, pvar = prev
+            if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == color.device and pc.dtype == torch.float32
+                    and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
+                raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {color.device}")
+            if not (torch.is_tensor(pvar) and tuple(pvar.shape) in ((h, w), (1, h, w))):
+                raise ValueError(f"prev's variance must be a float32 tensor of shape {(h, w)} on {color.device}")
+            plane(pvar, "prev's variance", tuple(pvar.shape))
+            pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
+            pv = _lib.mm_temporal_prev_var(pc.data_ptr(), self._aov_frames(pa, 1, h, w, color.device, "prev's aov"),
+                                           _lib.mm_camera.from_buffer_copy(pcam.tobytes()), pvar.data_ptr())
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
+        self._check(lib().mm_accumulate_frames_var(self._ctx, C.byref(uniform), cams.ctypes.data, color.data_ptr(),
+                                                   C.byref(a), vmean.data_ptr(),
+                                                   None if weight is None else weight.data_ptr(),
+                                                   None if pv is None else C.byref(pv), C.byref(p), n, x0, y0, w, h,
+                                                   out.data_ptr(), var_out.data_ptr()))
+        return out, var_out
+
     # -- pixel lists -----------------------------------------------------------
     def _pixel_list(self, pixels):
         """The (n, 2) int32 CUDA tensor of a pixel list: `pixels` itself, or an
@@ -563,6 +634,84 @@ class Renderer:
         extra, _ = self.trace_pixels(u, e, pixels)
         self.blend_pixels(acc, pixels, extra, extra_spp / ext.spp, x0, y0)
         return acc, n
+
+    def blend_pixels_var(self, image, var, pixels, extra, extra_vmean, m: float, x0: int = 0, y0: int = 0):
+        """blend_pixels() with the variance image beside the colour, both in
+        place (mm_blend_pixels_var).  `image`, `pixels`, `extra`, `m`, the
+        window: as in blend_pixels(); `var`: the (h, w) float32 CUDA tensor
+        accumulate_var returned beside `image`; `extra_vmean`: (n,) float32, the
+        variance of each entry's extra MEAN (trace_pixels_var's var / extra
+        spp).  The colours are blend_pixels()' bit for bit.  Returns (image,
+        var)."""
+        import torch
+
+        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
+                and image.dim() == 3 and image.shape[-1] == 4):
+            raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
+        h, w = image.shape[:2]
+        if not (torch.is_tensor(var) and var.is_cuda and var.device == image.device and var.dtype == torch.float32
+                and var.is_contiguous() and tuple(var.shape) == (h, w)):
+            raise ValueError(f"var must be a contiguous float32 ({h}, {w}) tensor on {image.device}")
+        pixels = self._pixel_list(pixels)
+        n = pixels.shape[0]
+        if not (torch.is_tensor(extra) and extra.is_cuda and extra.device == image.device
+                and extra.dtype == torch.float32 and extra.is_contiguous() and tuple(extra.shape) == (n, 4)):
+            raise ValueError(f"extra must be a contiguous float32 ({n}, 4) tensor on {image.device}")
+        if not (torch.is_tensor(extra_vmean) and extra_vmean.is_cuda and extra_vmean.device == image.device
+                and extra_vmean.dtype == torch.float32 and extra_vmean.is_contiguous()
+                and tuple(extra_vmean.shape) == (n,)):
+            raise ValueError(f"extra_vmean must be a contiguous float32 ({n},) tensor on {image.device}")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
+        self._check(lib().mm_blend_pixels_var(self._ctx, image.data_ptr(), var.data_ptr(), x0, y0, w, h,
+                                              pixels.data_ptr() if n else None, extra.data_ptr() if n else None,
+                                              extra_vmean.data_ptr() if n else None, n, float(m)))
+        return image, var
+
+    def top_up_var(self, uniform: _lib.mm_uniform, camera, ext: _lib.mm_ext, acc, var, aov, extra_spp: int,
+                   frame_key: int, n_min=None, rel_tol=None, x0: int = 0, y0: int = 0):
+        """top_up() for a frame of accumulate_var: spend extra samples where the
+        history is short, where the accumulated pixel is noisy, or both.
+        `acc`, `var`: ONE (h, w, 4) frame and its (h, w) variance as
+        accumulate_var returned them for the window (x0, y0, w, h), traced with
+        `camera` and `ext`; `aov`: that frame's guides (its "id" buffer).  The
+        selection is the union of select_short_history(acc, ids, n_min) and
+        select_noisy(acc, var, 1.0, rel_tol, ids=ids) -- `var` is already the
+        variance of the mean -- in row-major order; at least one of n_min and
+        rel_tol must be given.  The selected pixels are traced with extra_spp
+        (>= 2) samples each by trace_pixels_var (RNG frame `frame_key`, as in
+        top_up()) and blended by blend_pixels_var with extra_vmean = the extra
+        samples' variance / extra_spp and weight extra_spp / ext.spp, in place.
+        Returns (acc, var, n_selected); nothing is launched for 0."""
+        import torch
+
+        if n_min is None and rel_tol is None:
+            raise ValueError("top_up_var needs n_min, rel_tol or both")
+        if acc.dim() != 3 or acc.shape[-1] != 4 or tuple(var.shape) != tuple(acc.shape[:2]):
+            raise ValueError("acc must be one (h, w, 4) frame and var its (h, w) variance")
+        ids = aov["id"] if isinstance(aov, dict) else aov
+        lists = []
+        if n_min is not None:
+            lists.append(select_short_history(acc, ids, n_min, x0, y0))
+        if rel_tol is not None:
+            lists.append(select_noisy(acc, var, 1.0, rel_tol, ids=ids, x0=x0, y0=y0))
+        pixels = lists[0]
+        if len(lists) == 2:  # the union, row-major, each pixel once (x, y < 2^24)
+            both = torch.cat(lists).long()
+            key = torch.unique((both[:, 1] << 32) | both[:, 0])  # sorted
+            pixels = torch.stack((key & 0xFFFFFFFF, key >> 32), dim=1).to(torch.int32).contiguous()
+        n = int(pixels.shape[0])
+        if n == 0:
+            return acc, var, 0
+        u = _lib.mm_uniform.from_buffer_copy(bytes(uniform))
+        u.cam = _lib.mm_camera.from_buffer_copy(self._cameras([camera] if not isinstance(camera, np.ndarray)
+                                                              else camera.reshape(1, -1)).tobytes())
+        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
+                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        extra, var_b, _ = self.trace_pixels_var(u, e, pixels)
+        self.blend_pixels_var(acc, var, pixels, extra, (var_b / float(extra_spp)).contiguous(), extra_spp / ext.spp,
+                              x0, y0)
+        return acc, var, n
 
     # -- per-pixel sample variance ------------------------------------------------
     def trace_tile_var(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, x0: int, y0: int, w: int, h: int,

@@ -14,6 +14,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 32 --frames 40 --denoise-var    # + frame_NNNN_dnv.png: the variance-guided filter
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate     # + frame_NNNN_acc.png beside each frame
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate --top-up 2:24   # + extra samples where the history is short
+    python scripts/flythrough.py --maze 32 --frames 40 --accumulate-var --denoise-var   # + frame_NNNN_accv.png, and the variance-guided filter on it
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
@@ -57,7 +58,23 @@ Renderer.denoise_var (mm_denoise_frames_var, its defaults), whose luminance stop
 follows each pixel's own noise.  The frames are then traced one by one through
 Renderer.trace_tile_var, as with --refine, and with --refine the filter runs on
 the refined frames with the variance and the sample counts the rounds left.  Not
-with --accumulate: mm_accumulate_frames carries no variance through the history.
+with --accumulate: mm_accumulate_frames carries no variance through the history
+(--accumulate-var does).
+
+--accumulate-var, a mode of its own (not with --accumulate), also writes
+frame_NNNN_accv.png beside each frame: the frame through Renderer.accumulate_var
+(mm_accumulate_frames_var, its defaults), the accumulation of --accumulate with
+the variance of every accumulated pixel carried beside it.  The batch is traced
+with its per-pixel sample variance, in one Renderer.trace_tile_var launch where
+a multi-frame variance launch runs (2^24 .. 2^29 paths: tail deferral on, the
+staged paths of a launch), else (and with --refine) frame by frame.
+It composes with --denoise (the denoiser runs on the accumulated frames), with
+--denoise-var (the filter takes the accumulated variance, count 1, at sigma_l 2:
+the sweep of profiles/temporal_var/quality.txt), with
+--top-up N[:SPP] (through Renderer.top_up_var: mm_trace_pixels_var +
+mm_blend_pixels_var, SPP at least 2, RNG frame 2^21 + f) and with --refine (every
+frame is refined first and enters with weight = count / --spp per pixel and
+vmean = var / count).
 
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
@@ -72,6 +89,7 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "mirror-maze_amd"))
 sys.path.insert(0, str(REPO))
 
+ACCV_SIGMA_L = 2.0  # --accumulate-var --denoise-var: the filter's sigma_l on the accumulated variance
 
 def key_script(n_frames: int, turn_every: int, turn_dx: float):
     """(keys, mouse_dx) per frame: W held down, a mouse move of turn_dx on every
@@ -106,8 +124,12 @@ def main(argv=None) -> int:
     ap.add_argument("--accumulate", action="store_true",
                     help="also write frame_NNNN_acc.png: the frame through Renderer.accumulate (temporal accumulation); "
                          "with --denoise the denoiser runs on the accumulated frames")
+    ap.add_argument("--accumulate-var", action="store_true",
+                    help="also write frame_NNNN_accv.png: the frame through Renderer.accumulate_var (temporal "
+                         "accumulation that carries each pixel's variance); composes with --denoise, --denoise-var, "
+                         "--top-up and --refine, not with --accumulate")
     ap.add_argument("--top-up", metavar="N[:SPP]", default=None,
-                    help="with --accumulate: give the pixels whose history is shorter than N frames SPP more samples "
+                    help="with --accumulate or --accumulate-var: give the pixels whose history is shorter than N frames SPP more samples "
                          "(default 3 x --spp) and blend them into the accumulated frame")
     ap.add_argument("--refine", metavar="TOL[:SPP[:ROUNDS]]", default=None,
                     help="also write frame_NNNN_ref.png: up to ROUNDS (default 2) rounds of SPP more samples (default "
@@ -116,14 +138,17 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
         ap.error("--frames and --batch must be positive")
+    if a.accumulate and a.accumulate_var:
+        ap.error("--accumulate-var is a mode of its own: not with --accumulate")
     if a.denoise_var and a.accumulate:
-        ap.error("--denoise-var does not go with --accumulate: no variance is carried through the accumulated history")
-    if a.denoise_var and a.spp < 2:
-        ap.error("--denoise-var needs --spp of at least 2 (a sample variance)")
+        ap.error("--denoise-var does not go with --accumulate: no variance is carried through the accumulated history "
+                 "(--accumulate-var carries it)")
+    if (a.denoise_var or a.accumulate_var) and a.spp < 2:
+        ap.error("--denoise-var and --accumulate-var need --spp of at least 2 (a sample variance)")
     top_up = None  # (n_min, extra spp)
     if a.top_up is not None:
-        if not a.accumulate:
-            ap.error("--top-up needs --accumulate")
+        if not (a.accumulate or a.accumulate_var):
+            ap.error("--top-up needs --accumulate or --accumulate-var")
         try:
             n_min, _, extra = a.top_up.partition(":")
             top_up = (float(n_min), int(extra) if extra else 3 * a.spp)
@@ -131,10 +156,12 @@ def main(argv=None) -> int:
             ap.error("--top-up takes N[:SPP]")
         if not (top_up[0] > 1.0 and 1 <= top_up[1] <= 4096):
             ap.error("--top-up: N must be above 1 and SPP in 1..4096")
+        if a.accumulate_var and top_up[1] < 2:
+            ap.error("--top-up with --accumulate-var: SPP must be at least 2 (a sample variance)")
     refine = None  # (rel_tol, extra spp, rounds)
     if a.refine is not None:
         if a.accumulate:
-            ap.error("--refine does not go with --accumulate")
+            ap.error("--refine does not go with --accumulate (it goes with --accumulate-var)")
         try:
             parts = a.refine.split(":")
             if not 1 <= len(parts) <= 3:
@@ -160,21 +187,34 @@ def main(argv=None) -> int:
     import numpy as np
     import torch
 
-    from mirror_maze import Renderer, make_ext, mm_camera, mm_uniform
+    from mirror_maze import MMError, Renderer, make_ext, mm_camera, mm_uniform
     from mirror_maze.io import quantize, write_png
 
     out_dir = Path(a.out)
     out_dir.mkdir(parents=True, exist_ok=True)
     u = player.uniform()  # view size and chunk width; its camera is not used
-    with_var = refine is not None or a.denoise_var  # the frames are traced with their per-pixel sample variance
+    with_var = refine is not None or a.denoise_var or a.accumulate_var  # the frames are traced with their per-pixel sample variance
     floats = a.denoise or a.accumulate or with_var  # the batch is traced as float frames
-    prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera
+    prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera (-var: and its variance)
     with Renderer(0) as r:
         r.upload_scene(scene)
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
-            if with_var:
+            # one launch for the batch where a multi-frame variance call runs: at most the 2^29 paths a launch
+            # stages, and the tail deferral such a launch needs (from MM_OPT_DEFER_MIN's 2^24 paths on, where the
+            # plan has it; the call refuses the launch otherwise, before anything is enqueued)
+            paths = len(batch) * a.width * a.height * a.spp
+            one_var_launch = a.accumulate_var and refine is None and len(batch) > 1 and 2**24 <= paths <= 2**29
+            if one_var_launch:
+                try:
+                    img, var, _ = r.trace_tile_var(u, e, 0, 0, a.width, a.height, cameras=batch)
+                    count = torch.full_like(var, float(a.spp))
+                except MMError:
+                    one_var_launch = False
+            if one_var_launch:
+                pass
+            elif with_var:
                 # frame by frame (a single-frame variance call runs at any size; frame k is the batch launch's)
                 img = torch.empty((len(batch), a.height, a.width, 4), dtype=torch.float32, device="cuda:0")
                 var = torch.empty((len(batch), a.height, a.width), dtype=torch.float32, device="cuda:0")
@@ -192,7 +232,7 @@ def main(argv=None) -> int:
             r.sync()
             for k in range(len(batch)):
                 write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
-            print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if with_var else 'one launch'}, "
+            print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if with_var and not one_var_launch else 'one launch'}, "
                   f"{out_dir}/frame_{f0:04d}.png ...", flush=True)
             if refine:
                 for k in range(len(batch)):
@@ -209,7 +249,7 @@ def main(argv=None) -> int:
                 r.sync()
                 for k in range(len(batch)):
                     write_png(out_dir / f"frame_{f0 + k:04d}_ref.png", done[k])
-            if a.aov is None and not (a.denoise or a.denoise_var or a.accumulate):
+            if a.aov is None and not (a.denoise or a.denoise_var or a.accumulate or a.accumulate_var):
                 continue
             bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
                                want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
@@ -227,12 +267,35 @@ def main(argv=None) -> int:
             elif a.accumulate:
                 img = r.accumulate(u, batch, img, bufs, prev=prev)
                 prev = (img[-1], {k: v[-1:] for k, v in bufs.items()}, batch[-1])
-            if a.accumulate:
+            if a.accumulate_var:
+                vmean = (var / count).contiguous()  # the variance of each frame's pixel mean
+                weight = (count / float(a.spp)).contiguous() if refine else None  # refined pixels hold more samples
+                if top_up:
+                    # frame by frame: the history of frame k is the topped-up frame k - 1
+                    acc_img, acc_var = torch.empty_like(img), torch.empty_like(var)
+                    for k in range(len(batch)):
+                        gk = {name: v[k:k + 1] for name, v in bufs.items()}
+                        r.accumulate_var(u, batch[k:k + 1], img[k:k + 1], gk, vmean[k:k + 1],
+                                         None if weight is None else weight[k:k + 1], prev=prev, out=acc_img[k:k + 1],
+                                         var_out=acc_var[k:k + 1])
+                        _, _, n_sel = r.top_up_var(u, batch[k], e, acc_img[k], acc_var[k], gk, top_up[1],
+                                                   2**21 + f0 + k, n_min=top_up[0])
+                        print(f"# frame {f0 + k}: topped up {n_sel} pixels "
+                              f"({100.0 * n_sel / (a.width * a.height):.2f} %) with {top_up[1]} spp", flush=True)
+                        prev = (acc_img[k], gk, batch[k], acc_var[k])
+                    img = acc_img
+                else:
+                    img, acc_var = r.accumulate_var(u, batch, img, bufs, vmean, weight, prev=prev)
+                    prev = (img[-1], {k: v[-1:] for k, v in bufs.items()}, batch[-1], acc_var[-1])
+                var, count = acc_var, 1.0  # what --denoise-var filters with: already the variance of the mean
+            if a.accumulate or a.accumulate_var:
+                tag = "accv" if a.accumulate_var else "acc"
                 acc = r.quantize(img).cpu().numpy()
                 r.sync()
                 for k in range(len(batch)):
-                    write_png(out_dir / f"frame_{f0 + k:04d}_acc.png", acc[k])
-                print(f"# frames {f0}..{f0 + len(batch) - 1}: accumulated, {out_dir}/frame_{f0:04d}_acc.png ...", flush=True)
+                    write_png(out_dir / f"frame_{f0 + k:04d}_{tag}.png", acc[k])
+                print(f"# frames {f0}..{f0 + len(batch) - 1}: accumulated, {out_dir}/frame_{f0:04d}_{tag}.png ...",
+                      flush=True)
             if a.denoise:
                 clean = r.denoise(img, bufs, rgba8=True).cpu().numpy()
                 r.sync()
@@ -240,7 +303,10 @@ def main(argv=None) -> int:
                     write_png(out_dir / f"frame_{f0 + k:04d}_dn.png", clean[k])
                 print(f"# frames {f0}..{f0 + len(batch) - 1}: denoised, {out_dir}/frame_{f0:04d}_dn.png ...", flush=True)
             if a.denoise_var:
-                clean = r.denoise_var(img, bufs, var, count, rgba8=True).cpu().numpy()
+                # on an accumulated variance the narrow stop wins (profiles/temporal_var/quality.txt: sigma_l 2 has
+                # the least geometric mean over the maze and the corridor, walk and turn); else the call's default
+                kw = dict(sigma_l=ACCV_SIGMA_L) if a.accumulate_var else {}
+                clean = r.denoise_var(img, bufs, var, count, rgba8=True, **kw).cpu().numpy()
                 r.sync()
                 for k in range(len(batch)):
                     write_png(out_dir / f"frame_{f0 + k:04d}_dnv.png", clean[k])
