@@ -28,12 +28,6 @@ struct mm_comm {
 
 namespace {
 
-#define HIPC(ctx, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) return ctx_fail((ctx), MM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 #define NCCLC(ctx, comm, expr)                                                                            \
     do {                                                                                                  \
         ncclResult_t _r = (expr);                                                                         \

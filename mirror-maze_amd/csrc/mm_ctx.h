@@ -1,10 +1,12 @@
 // mm_ctx.h — the context behind the C ABI's opaque mm_ctx (include/mm_api.h),
-// shared by the runtime (mm_runtime.hip) and the multi-GPU frame path
-// (mm_comm.hip).  Private to the library.
+// shared by the runtime (mm_runtime.hip), the frame filters' calls
+// (mm_filters.hip) and the multi-GPU frame path (mm_comm.hip), with the three
+// files' error plumbing (fail, HIPC, ensure).  Private to the library.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -65,7 +67,7 @@ struct mm_ctx {
     float* h_cams = nullptr;
     float* d_cams = nullptr;
     size_t cams_cap = 0, cams_next = 0;
-    // mm_denoise_frames' scratch: the two intermediate images a frame's passes alternate between (one frame
+    // mm_denoise_frames' scratch (mm_filters.hip dn_begin): the two intermediate images a frame's passes alternate between (one frame
     // each, `dn_img_cap` pixels in all) and the call's packed key records (`dn_keys_cap`).  A call's kernels are
     // ordered after the last call's on the same stream; `dn_done` (recorded after every call) orders them when
     // the stream changed.  mm_denoise_frames_var shares all of it, under the same bookkeeping, and keeps the
@@ -132,5 +134,24 @@ namespace mm {
 inline int ctx_fail(mm_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
+}
+inline int fail(mm_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
+
+// Return MM_ERR_HIP from the calling function, with the runtime's message, if a HIP call fails.
+#define HIPC(ctx, expr)                                                                               \
+    do {                                                                                              \
+        hipError_t _e = (expr);                                                                       \
+        if (_e != hipSuccess)                                                                         \
+            return mm::ctx_fail((ctx), MM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// A device array of at least `n` elements: kept if it is large enough, else freed and allocated anew.
+template <typename T>
+int ensure(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
+    if (n <= cap && ptr) return MM_OK;
+    if (ptr) { (void)hipFree(ptr); ptr = nullptr; cap = 0; }
+    HIPC(c, hipMalloc((void**)&ptr, std::max<size_t>(n, 1) * sizeof(T)));
+    cap = n;
+    return MM_OK;
 }
 }  // namespace mm

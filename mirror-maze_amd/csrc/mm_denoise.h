@@ -1,6 +1,6 @@
-// mm_denoise.h — what the two a-trous pass kernels share (denoise_kernels.hip: mm_denoise_frames;
-// denoise_var_kernels.hip: mm_denoise_frames_var): the luminance, the packed key read, the three-clause
-// surface test and the guarded quotient with its range tests.  Device code only.
+// mm_denoise.h — the pieces of the a-trous pass kernel (denoise_kernels.hip: mm_denoise_frames and, as its kVar
+// instances, mm_denoise_frames_var): the luminance, the packed key read, the three-clause surface test and the
+// guarded quotient with its range tests.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// mm_launch.h — host-callable launchers for the kernels in trace_*.hip.
+// mm_launch.h — host-callable launchers for the kernels in trace_kernels.hip, display.hip, denoise_kernels.hip
+// and temporal_kernels.hip, and the argument structs they take.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -166,7 +167,9 @@ struct DnPass {
 hipError_t launch_denoise_keys(const float4* al, const uint32_t* id, uint2* keys, size_t n, hipStream_t s);
 hipError_t launch_denoise_pass(const DnPass& pass, hipStream_t s);
 
-// One pass of mm_denoise_frames_var over one frame (denoise_var_kernels.hip); every pointer points at that frame.
+// One pass of mm_denoise_frames_var over one frame (denoise_kernels.hip, the kVar instances); every pointer points
+// at that frame.  The members it shares with DnPass have DnPass's names (the pass templates take either), and the
+// layout is the one its instances were measured with.
 struct DnVarPass {
     const float4* in = nullptr;      // the pass's input image
     const float* vin = nullptr;      // the pass's input variance (of the pixel mean's luminance)
@@ -211,7 +214,7 @@ struct TpBlend {
 };
 hipError_t launch_blend_pixels(const TpBlend& blend, hipStream_t s);
 
-// One frame of mm_accumulate_frames_var (temporal_var_kernels.hip): TpFrame, and the variances beside it.
+// One frame of mm_accumulate_frames_var (temporal_kernels.hip, kVar): TpFrame, and the variances beside it.
 struct TpFrameVar {
     TpFrame f;                       // as for mm_accumulate_frames
     const float* vmean = nullptr;    // the frame's variance of the pixel mean's luminance
@@ -221,7 +224,7 @@ struct TpFrameVar {
 };
 hipError_t launch_temporal_frame_var(const TpFrameVar& frame, hipStream_t s);
 
-// mm_blend_pixels_var (temporal_var_kernels.hip): TpBlend, and the variance image beside it.
+// mm_blend_pixels_var (temporal_kernels.hip, kVar): TpBlend, and the variance image beside it.
 struct TpBlendVar {
     TpBlend b;                          // as for mm_blend_pixels
     float* var = nullptr;               // the window's w * h variances, updated in place

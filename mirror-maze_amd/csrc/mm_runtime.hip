@@ -1,4 +1,5 @@
-// mm_runtime.hip — the C ABI of include/mm_api.h over the HIP runtime.
+// mm_runtime.hip — the C ABI of include/mm_api.h over the HIP runtime (the
+// frame filters' six calls: mm_filters.hip; the multi-GPU path: mm_comm.hip).
 //
 // Replaces the reference's Metal plumbing: device/queue creation
 // (src/main.rs:616-626), buffer creation and updates (src/utils.rs:86-102,
@@ -22,6 +23,7 @@
 #include "mm_aov.h"
 #include "mm_api.h"
 #include "mm_ctx.h"
+#include "mm_filter_args.h"
 #include "mm_launch.h"
 #include "mm_plan.h"
 
@@ -35,24 +37,6 @@ size_t build_compact_rects(const mm_rect* rects, uint32_t n_rects, const uint32_
 constexpr uint32_t kStatusSlots = 1024;
 
 namespace {
-
-int fail(mm_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
-
-#define HIPC(ctx, expr)                                                                           \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess)                                                                     \
-            return fail((ctx), MM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename T>
-int ensure(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
-    if (n <= cap && ptr) return MM_OK;
-    if (ptr) { (void)hipFree(ptr); ptr = nullptr; cap = 0; }
-    HIPC(c, hipMalloc((void**)&ptr, std::max<size_t>(n, 1) * sizeof(T)));
-    cap = n;
-    return MM_OK;
-}
 
 DevScene dev_scene(const mm_ctx* c) {
     DevScene s;
@@ -187,21 +171,6 @@ int stage_cameras(mm_ctx* c, const mm_camera* cams, uint32_t n, const float*& de
     c->cams_next += n;
     dev = d;
     return MM_OK;
-}
-
-// Whether [a, a + na) and [b, b + nb) share a byte.
-bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
-// mm_denoise_frames' and mm_denoise_frames_var's scratch of at least `n` elements: grown (never shrunk) after everything the device has
-// queued is done -- an earlier call's passes may still read the old one, on any stream used so far.
-template <typename T>
-int dn_scratch(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
-    if (n <= cap && ptr) return MM_OK;
-    HIPC(c, hipDeviceSynchronize());
-    return ensure(c, ptr, cap, n);
 }
 
 int begin_timing(mm_ctx* c) {
@@ -698,311 +667,6 @@ int mm_quantize_rgba8(mm_ctx* c, const float* rgba_dev, uint8_t* rgba8_dev, uint
     return MM_OK;
 }
 
-int mm_denoise_frames(mm_ctx* c, const float* color_dev, const mm_aov* guides, const mm_denoise_params* p,
-                      uint32_t n_frames, uint32_t w, uint32_t h, void* out_dev) {
-    // (argument checks first, and none of them needs the context: a binding can be tested without a GPU)
-    if (!p || !guides || !color_dev || !out_dev) return fail(c, MM_ERR_INVALID, "mm_denoise_frames: null argument");
-    if (!guides->normal_depth || !guides->albedo || !guides->id)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames: all three guide buffers are required");
-    if (p->n_passes < 1 || p->n_passes > MM_DENOISE_MAX_PASSES)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames: n_passes must be 1..8");
-    if (p->flags & ~MM_DN_RGBA8) return fail(c, MM_ERR_INVALID, "mm_denoise_frames: unknown flags");
-    if (w == 0 || h == 0 || n_frames == 0) return fail(c, MM_ERR_INVALID, "mm_denoise_frames: empty tile or no frames");
-    const bool rgba8 = (p->flags & MM_DN_RGBA8) != 0;
-    if (reinterpret_cast<uintptr_t>(color_dev) % 16 || reinterpret_cast<uintptr_t>(guides->normal_depth) % 16 ||
-        reinterpret_cast<uintptr_t>(guides->albedo) % 16 || reinterpret_cast<uintptr_t>(guides->id) % 4 ||
-        reinterpret_cast<uintptr_t>(out_dev) % (rgba8 ? 4 : 16))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames: misaligned buffer (float4: 16 bytes, id and RGBA8: 4)");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames: more pixels than one call holds");
-    const uint64_t n_all = n_pix * n_frames, out_bytes = n_all * (rgba8 ? 4 : 16);
-    if (ranges_overlap(out_dev, out_bytes, color_dev, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->normal_depth, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->albedo, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->id, n_all * 4))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames: the output overlaps an input");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    const uint32_t n_passes = p->n_passes;
-    // All passes of a frame run before the next frame's: the two intermediate images are one frame each (a
-    // launch per pass over all frames measured 1.4 % slower and needs 2 x n_frames images).
-    if (n_passes > 1)
-        if (int rc = dn_scratch(c, c->d_dn_img, c->dn_img_cap, (n_passes > 2 ? 2 : 1) * (size_t)n_pix)) return rc;
-    if (int rc = dn_scratch(c, c->d_dn_keys, c->dn_keys_cap, (size_t)n_all)) return rc;
-    if (!c->dn_done) HIPC(c, hipEventCreateWithFlags(&c->dn_done, hipEventDisableTiming));
-    if (c->dn_pending && c->dn_stream != c->stream) HIPC(c, hipStreamWaitEvent(c->stream, c->dn_done, 0));
-    const float4* color = reinterpret_cast<const float4*>(color_dev);
-    HIPC(c, launch_denoise_keys(reinterpret_cast<const float4*>(guides->albedo), guides->id, c->d_dn_keys,
-                                (size_t)n_all, c->stream));
-    c->dn_pending = true;
-    c->dn_stream = c->stream;
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const size_t o = (size_t)f * n_pix;
-        DnPass a;
-        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
-        a.keys = c->d_dn_keys + o;
-        a.w = w; a.h = h;
-        a.sigma_z = p->sigma_z; a.sigma_l = p->sigma_l;
-        a.in = color + o;
-        for (uint32_t i = 0; i < n_passes; ++i) {
-            const bool last = i + 1 == n_passes;
-            a.s = 1u << i;
-            a.sl = p->sigma_l * (1.0f / (float)a.s);
-            a.rgba8 = last && rgba8;
-            if (last) a.out = rgba8 ? (void*)(reinterpret_cast<uint8_t*>(out_dev) + o * 4)
-                                    : (void*)(reinterpret_cast<float4*>(out_dev) + o);
-            else a.out = c->d_dn_img + (size_t)(i & 1u) * n_pix;
-            HIPC(c, launch_denoise_pass(a, c->stream));
-            a.in = reinterpret_cast<const float4*>(a.out);
-        }
-    }
-    HIPC(c, hipEventRecord(c->dn_done, c->stream));
-    return MM_OK;
-}
-
-int mm_denoise_frames_var(mm_ctx* c, const float* color_dev, const mm_aov* guides, const float* vmean_dev,
-                          const mm_denoise_var_params* p, uint32_t n_frames, uint32_t w, uint32_t h, void* out_dev,
-                          float* var_out_dev) {
-    // (argument checks first, and none of them needs the context, as in mm_denoise_frames)
-    if (!p || !guides || !color_dev || !vmean_dev || !out_dev)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: null argument");
-    if (!guides->normal_depth || !guides->albedo || !guides->id)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: all three guide buffers are required");
-    if (p->n_passes < 1 || p->n_passes > MM_DENOISE_MAX_PASSES)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: n_passes must be 1..8");
-    if (p->flags & ~MM_DNV_RGBA8) return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: unknown flags");
-    if (p->reserved != 0) return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: reserved must be 0");
-    if (p->sigma_l > 0.0f && (!(p->eps_l > 0.0f) || !std::isfinite(p->eps_l)))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: eps_l must be positive and finite when sigma_l > 0");
-    if (w == 0 || h == 0 || n_frames == 0)
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: empty tile or no frames");
-    const bool rgba8 = (p->flags & MM_DNV_RGBA8) != 0;
-    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
-    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
-        misaligned(guides->id, 4) || misaligned(vmean_dev, 4) || misaligned(out_dev, rgba8 ? 4 : 16) ||
-        misaligned(var_out_dev, 4))
-        return fail(c, MM_ERR_INVALID,
-                    "mm_denoise_frames_var: misaligned buffer (float4: 16 bytes; id, variance and RGBA8: 4)");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: more pixels than one call holds");
-    const uint64_t n_all = n_pix * n_frames, out_bytes = n_all * (rgba8 ? 4 : 16);
-    const struct { const void* ptr; uint64_t bytes; } inputs[] = {
-        {color_dev, n_all * 16}, {guides->normal_depth, n_all * 16}, {guides->albedo, n_all * 16},
-        {guides->id, n_all * 4}, {vmean_dev, n_all * 4}};
-    for (const auto& in : inputs)
-        if (ranges_overlap(out_dev, out_bytes, in.ptr, in.bytes) ||
-            (var_out_dev && ranges_overlap(var_out_dev, n_all * 4, in.ptr, in.bytes)))
-            return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: an output overlaps an input");
-    if (var_out_dev && ranges_overlap(var_out_dev, n_all * 4, out_dev, out_bytes))
-        return fail(c, MM_ERR_INVALID, "mm_denoise_frames_var: the two outputs overlap");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    const uint32_t n_passes = p->n_passes;
-    // The scratch, its event and its stream bookkeeping are mm_denoise_frames': calls of the two functions take
-    // turns on it in the order they were made.
-    if (n_passes > 1) {
-        const size_t sides = n_passes > 2 ? 2 : 1;
-        if (int rc = dn_scratch(c, c->d_dn_img, c->dn_img_cap, sides * (size_t)n_pix)) return rc;
-        if (int rc = dn_scratch(c, c->d_dn_var, c->dn_var_cap, sides * (size_t)n_pix)) return rc;
-    }
-    if (int rc = dn_scratch(c, c->d_dn_keys, c->dn_keys_cap, (size_t)n_all)) return rc;
-    if (!c->dn_done) HIPC(c, hipEventCreateWithFlags(&c->dn_done, hipEventDisableTiming));
-    if (c->dn_pending && c->dn_stream != c->stream) HIPC(c, hipStreamWaitEvent(c->stream, c->dn_done, 0));
-    const float4* color = reinterpret_cast<const float4*>(color_dev);
-    HIPC(c, launch_denoise_keys(reinterpret_cast<const float4*>(guides->albedo), guides->id, c->d_dn_keys,
-                                (size_t)n_all, c->stream));
-    c->dn_pending = true;
-    c->dn_stream = c->stream;
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const size_t o = (size_t)f * n_pix;
-        DnVarPass a;
-        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
-        a.keys = c->d_dn_keys + o;
-        a.w = w; a.h = h;
-        a.sigma_z = p->sigma_z; a.sigma_l = p->sigma_l; a.eps_l = p->eps_l;
-        a.in = color + o;
-        a.vin = vmean_dev + o;
-        for (uint32_t i = 0; i < n_passes; ++i) {
-            const bool last = i + 1 == n_passes;
-            a.s = 1u << i;
-            a.rgba8 = last && rgba8;
-            if (last) {
-                a.out = rgba8 ? (void*)(reinterpret_cast<uint8_t*>(out_dev) + o * 4)
-                              : (void*)(reinterpret_cast<float4*>(out_dev) + o);
-                a.vout = var_out_dev ? var_out_dev + o : nullptr;
-            } else {
-                a.out = c->d_dn_img + (size_t)(i & 1u) * n_pix;
-                a.vout = c->d_dn_var + (size_t)(i & 1u) * n_pix;
-            }
-            HIPC(c, launch_denoise_var_pass(a, c->stream));
-            a.in = reinterpret_cast<const float4*>(a.out);
-            a.vin = a.vout;
-        }
-    }
-    HIPC(c, hipEventRecord(c->dn_done, c->stream));
-    return MM_OK;
-}
-
-int mm_accumulate_frames(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const float* color_dev,
-                         const mm_aov* guides, const mm_temporal_prev* prev, const mm_temporal_params* p,
-                         uint32_t n_frames, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out_dev) {
-    // (argument checks first, and none of them needs the context, as in mm_denoise_frames)
-    if (!u || !cams || !color_dev || !guides || !p || !out_dev)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: null argument");
-    if (!guides->normal_depth || !guides->albedo || !guides->id)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: all three guide buffers are required");
-    if (prev && (!prev->color || !prev->guides.normal_depth || !prev->guides.albedo || !prev->guides.id))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: prev needs its colour and all three guide buffers");
-    if (p->n_max < 1 || p->n_max > 65535) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: n_max must be 1..65535");
-    if (!(p->tol_z > 0.0f) || !std::isfinite(p->tol_z))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: tol_z must be positive and finite");
-    if (!(p->w_min > 0.0f && p->w_min <= 1.0f))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: w_min must be in (0, 1]");
-    if (p->flags) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: unknown flags");
-    if (w == 0 || h == 0 || n_frames == 0)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: empty tile or no frames");
-    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
-    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
-        misaligned(guides->id, 4) || misaligned(out_dev, 16) ||
-        (prev && (misaligned(prev->color, 16) || misaligned(prev->guides.normal_depth, 16) ||
-                  misaligned(prev->guides.albedo, 16) || misaligned(prev->guides.id, 4))))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: misaligned buffer (float4: 16 bytes, id: 4)");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: more pixels than one call holds");
-    if ((uint64_t)x0 + w > (1ull << 24) || (uint64_t)y0 + h > (1ull << 24))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: the window ends beyond pixel 2^24");
-    const uint64_t n_all = n_pix * n_frames, out_bytes = n_all * 16;
-    if (ranges_overlap(out_dev, out_bytes, color_dev, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->normal_depth, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->albedo, n_all * 16) ||
-        ranges_overlap(out_dev, out_bytes, guides->id, n_all * 4) ||
-        (prev && (ranges_overlap(out_dev, out_bytes, prev->color, n_pix * 16) ||
-                  ranges_overlap(out_dev, out_bytes, prev->guides.normal_depth, n_pix * 16) ||
-                  ranges_overlap(out_dev, out_bytes, prev->guides.albedo, n_pix * 16) ||
-                  ranges_overlap(out_dev, out_bytes, prev->guides.id, n_pix * 4))))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames: the output overlaps an input");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    // One launch per frame, in stream order: frame f reads frame f - 1's output, which the kernel boundary makes
-    // visible.  The cameras travel in the launches' arguments, so `cams` is consumed when this returns and the
-    // call keeps no scratch.
-    TpFrame a;
-    a.view_w = u->view_w; a.view_h = u->view_h;
-    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
-    a.n_max = (float)p->n_max; a.tol_z = p->tol_z; a.w_min = p->w_min;
-    if (prev) {
-        a.h_color = reinterpret_cast<const float4*>(prev->color);
-        a.h_nd = reinterpret_cast<const float4*>(prev->guides.normal_depth);
-        a.h_al = reinterpret_cast<const float4*>(prev->guides.albedo);
-        a.h_id = prev->guides.id;
-        a.h_cam = prev->cam;
-    }
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const size_t o = (size_t)f * n_pix;
-        a.color = reinterpret_cast<const float4*>(color_dev) + o;
-        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
-        a.al = reinterpret_cast<const float4*>(guides->albedo) + o;
-        a.id = guides->id + o;
-        a.out = reinterpret_cast<float4*>(out_dev) + o;
-        a.cam = cams[f];
-        HIPC(c, launch_temporal_frame(a, c->stream));
-        a.h_color = a.out; a.h_nd = a.nd; a.h_al = a.al; a.h_id = a.id;
-        a.h_cam = a.cam;
-    }
-    return MM_OK;
-}
-
-int mm_accumulate_frames_var(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const float* color_dev,
-                             const mm_aov* guides, const float* vmean_dev, const float* weight_dev,
-                             const mm_temporal_prev_var* prev, const mm_temporal_params* p, uint32_t n_frames,
-                             uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, void* out_dev, float* var_out_dev) {
-    // (argument checks first, and none of them needs the context, as in mm_accumulate_frames)
-    if (!u || !cams || !color_dev || !guides || !vmean_dev || !p || !out_dev || !var_out_dev)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: null argument");
-    if (!guides->normal_depth || !guides->albedo || !guides->id)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: all three guide buffers are required");
-    if (prev && (!prev->color || !prev->guides.normal_depth || !prev->guides.albedo || !prev->guides.id || !prev->var))
-        return fail(c, MM_ERR_INVALID,
-                    "mm_accumulate_frames_var: prev needs its colour, all three guide buffers and its variance");
-    if (p->n_max < 1 || p->n_max > 65535)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: n_max must be 1..65535");
-    if (!(p->tol_z > 0.0f) || !std::isfinite(p->tol_z))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: tol_z must be positive and finite");
-    if (!(p->w_min > 0.0f && p->w_min <= 1.0f))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: w_min must be in (0, 1]");
-    if (p->flags) return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: unknown flags");
-    if (w == 0 || h == 0 || n_frames == 0)
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: empty tile or no frames");
-    auto misaligned = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a != 0; };
-    if (misaligned(color_dev, 16) || misaligned(guides->normal_depth, 16) || misaligned(guides->albedo, 16) ||
-        misaligned(guides->id, 4) || misaligned(out_dev, 16) || misaligned(vmean_dev, 4) ||
-        misaligned(weight_dev, 4) || misaligned(var_out_dev, 4) ||
-        (prev && (misaligned(prev->color, 16) || misaligned(prev->guides.normal_depth, 16) ||
-                  misaligned(prev->guides.albedo, 16) || misaligned(prev->guides.id, 4) || misaligned(prev->var, 4))))
-        return fail(c, MM_ERR_INVALID,
-                    "mm_accumulate_frames_var: misaligned buffer (float4: 16 bytes, id and variances: 4)");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (n_pix > 0x7FFFFFFFull || n_pix * n_frames > (1ull << 40))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: more pixels than one call holds");
-    if ((uint64_t)x0 + w > (1ull << 24) || (uint64_t)y0 + h > (1ull << 24))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: the window ends beyond pixel 2^24");
-    const uint64_t n_all = n_pix * n_frames;
-    // either output against every input and every prev buffer, and the two outputs against each other
-    auto hits_input = [&](const void* o, uint64_t bytes) {
-        return ranges_overlap(o, bytes, color_dev, n_all * 16) ||
-               ranges_overlap(o, bytes, guides->normal_depth, n_all * 16) ||
-               ranges_overlap(o, bytes, guides->albedo, n_all * 16) || ranges_overlap(o, bytes, guides->id, n_all * 4) ||
-               ranges_overlap(o, bytes, vmean_dev, n_all * 4) ||
-               (weight_dev && ranges_overlap(o, bytes, weight_dev, n_all * 4)) ||
-               (prev && (ranges_overlap(o, bytes, prev->color, n_pix * 16) ||
-                         ranges_overlap(o, bytes, prev->guides.normal_depth, n_pix * 16) ||
-                         ranges_overlap(o, bytes, prev->guides.albedo, n_pix * 16) ||
-                         ranges_overlap(o, bytes, prev->guides.id, n_pix * 4) ||
-                         ranges_overlap(o, bytes, prev->var, n_pix * 4)));
-    };
-    if (hits_input(out_dev, n_all * 16) || hits_input(var_out_dev, n_all * 4))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: an output overlaps an input");
-    if (ranges_overlap(out_dev, n_all * 16, var_out_dev, n_all * 4))
-        return fail(c, MM_ERR_INVALID, "mm_accumulate_frames_var: the two outputs overlap");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    // One launch per frame, in stream order, as mm_accumulate_frames: frame f reads frame f - 1's colour and
-    // variance outputs, which the kernel boundary makes visible; no scratch.
-    TpFrameVar b;
-    TpFrame& a = b.f;
-    a.view_w = u->view_w; a.view_h = u->view_h;
-    a.x0 = x0; a.y0 = y0; a.w = w; a.h = h;
-    a.n_max = (float)p->n_max; a.tol_z = p->tol_z; a.w_min = p->w_min;
-    if (prev) {
-        a.h_color = reinterpret_cast<const float4*>(prev->color);
-        a.h_nd = reinterpret_cast<const float4*>(prev->guides.normal_depth);
-        a.h_al = reinterpret_cast<const float4*>(prev->guides.albedo);
-        a.h_id = prev->guides.id;
-        a.h_cam = prev->cam;
-        b.h_var = prev->var;
-    }
-    for (uint32_t f = 0; f < n_frames; ++f) {
-        const size_t o = (size_t)f * n_pix;
-        a.color = reinterpret_cast<const float4*>(color_dev) + o;
-        a.nd = reinterpret_cast<const float4*>(guides->normal_depth) + o;
-        a.al = reinterpret_cast<const float4*>(guides->albedo) + o;
-        a.id = guides->id + o;
-        a.out = reinterpret_cast<float4*>(out_dev) + o;
-        a.cam = cams[f];
-        b.vmean = vmean_dev + o;
-        b.weight = weight_dev ? weight_dev + o : nullptr;
-        b.vout = var_out_dev + o;
-        HIPC(c, launch_temporal_frame_var(b, c->stream));
-        a.h_color = a.out; a.h_nd = a.nd; a.h_al = a.al; a.h_id = a.id;
-        a.h_cam = a.cam;
-        b.h_var = b.vout;
-    }
-    return MM_OK;
-}
-
 int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
     if (!c) return MM_ERR_INVALID;
     if (!c->d_fb) return fail(c, MM_ERR_INVALID, "mm_read_framebuffer: nothing rendered yet");
@@ -1334,80 +998,6 @@ int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint3
 int mm_trace_pixels_var(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
                         void* out_dev, float* var_dev, mm_stats* stats) {
     return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, true, var_dev);
-}
-
-int mm_blend_pixels(mm_ctx* c, float* image_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
-                    const uint32_t* pixels_dev, const float* extra_dev, uint64_t n_pixels, float m) {
-    // (argument checks first, and none of them needs the context, as in mm_accumulate_frames)
-    if (!image_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: null image");
-    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7FFFFFFFull)
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: empty window or more than 2^31 - 1 pixels");
-    if (!(m > 0.0f) || !std::isfinite(m)) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: m must be positive and finite");
-    if (reinterpret_cast<uintptr_t>(image_dev) % 16) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: misaligned image");
-    if (n_pixels == 0) return c ? MM_OK : MM_ERR_INVALID;
-    if (!pixels_dev || !extra_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: null argument");
-    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(extra_dev) % 16)
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: misaligned buffer (float4: 16 bytes, the list: 8)");
-    if (n_pixels > (1ull << 38)) return fail(c, MM_ERR_INVALID, "mm_blend_pixels: more entries than one launch holds");
-    if (ranges_overlap(image_dev, (uint64_t)w * h * 16, extra_dev, n_pixels * 16))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels: extra_dev overlaps the image");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    TpBlend b;
-    b.image = reinterpret_cast<float4*>(image_dev);
-    b.pixels = reinterpret_cast<const uint2*>(pixels_dev);
-    b.extra = reinterpret_cast<const float4*>(extra_dev);
-    b.n = n_pixels;
-    b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
-    b.m = m;
-    HIPC(c, launch_blend_pixels(b, c->stream));
-    return MM_OK;
-}
-
-int mm_blend_pixels_var(mm_ctx* c, float* image_dev, float* var_dev, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
-                        const uint32_t* pixels_dev, const float* extra_dev, const float* extra_vmean_dev,
-                        uint64_t n_pixels, float m) {
-    // (argument checks first, and none of them needs the context, as in mm_blend_pixels)
-    if (!image_dev || !var_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: null image or variance");
-    if (w == 0 || h == 0 || (uint64_t)w * h > 0x7FFFFFFFull)
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: empty window or more than 2^31 - 1 pixels");
-    if (!(m > 0.0f) || !std::isfinite(m))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: m must be positive and finite");
-    if (reinterpret_cast<uintptr_t>(image_dev) % 16 || reinterpret_cast<uintptr_t>(var_dev) % 4)
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: misaligned image or variance");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (ranges_overlap(image_dev, n_pix * 16, var_dev, n_pix * 4))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: var_dev overlaps the image");
-    if (n_pixels == 0) return c ? MM_OK : MM_ERR_INVALID;
-    if (!pixels_dev || !extra_dev || !extra_vmean_dev) return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: null argument");
-    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(extra_dev) % 16 ||
-        reinterpret_cast<uintptr_t>(extra_vmean_dev) % 4)
-        return fail(c, MM_ERR_INVALID,
-                    "mm_blend_pixels_var: misaligned buffer (float4: 16 bytes, the list: 8, variances: 4)");
-    if (n_pixels > (1ull << 38))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: more entries than one launch holds");
-    if (ranges_overlap(image_dev, n_pix * 16, extra_dev, n_pixels * 16) ||
-        ranges_overlap(image_dev, n_pix * 16, extra_vmean_dev, n_pixels * 4) ||
-        ranges_overlap(image_dev, n_pix * 16, pixels_dev, n_pixels * 8))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: an input overlaps the image");
-    if (ranges_overlap(var_dev, n_pix * 4, extra_dev, n_pixels * 16) ||
-        ranges_overlap(var_dev, n_pix * 4, extra_vmean_dev, n_pixels * 4) ||
-        ranges_overlap(var_dev, n_pix * 4, pixels_dev, n_pixels * 8))
-        return fail(c, MM_ERR_INVALID, "mm_blend_pixels_var: an input overlaps var_dev");
-    if (!c) return MM_ERR_INVALID;
-    HIPC(c, hipSetDevice(c->device));
-    TpBlendVar v;
-    TpBlend& b = v.b;
-    b.image = reinterpret_cast<float4*>(image_dev);
-    b.pixels = reinterpret_cast<const uint2*>(pixels_dev);
-    b.extra = reinterpret_cast<const float4*>(extra_dev);
-    b.n = n_pixels;
-    b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
-    b.m = m;
-    v.var = var_dev;
-    v.extra_vmean = extra_vmean_dev;
-    HIPC(c, launch_blend_pixels_var(v, c->stream));
-    return MM_OK;
 }
 
 namespace {

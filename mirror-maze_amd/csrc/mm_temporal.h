@@ -1,7 +1,7 @@
 // mm_temporal.h — the reprojection mm_accumulate_frames and mm_accumulate_frames_var share
 // (include/mm_api.h states the arithmetic): the rotation, the projection of a pixel's virtual image into
 // the history frame's camera, a tap's address and the key test that confirms or refutes it.  Device code,
-// included by temporal_kernels.hip and temporal_var_kernels.hip: both kernels run the same operations.
+// included by temporal_kernels.hip: the plain and the variance instances run the same operations.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -319,30 +319,15 @@ class Renderer:
         quantize() of the float result).  The inputs are not written."""
         import torch
 
-        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
-                and color.dim() in (3, 4) and color.shape[-1] == 4):
-            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
-        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
-        if not (isinstance(aov, dict) and all(k in aov for k in self.AOV_NAMES)):
-            raise ValueError(f"aov must hold the buffers {self.AOV_NAMES} of trace_aov")
-        for k in self.AOV_NAMES:
-            shape, dt = ((n, h, w), torch.int32) if k == "id" else ((n, h, w, 4), torch.float32)
-            t = aov[k]
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == color.device and t.dtype == dt
-                    and t.is_contiguous() and tuple(t.shape) == shape):
-                raise ValueError(f"aov[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {color.device}")
+        n, h, w = self._frames(color)
+        a = self._aov_frames(aov, n, h, w, color.device, "aov")
         if not 1 <= int(n_passes) <= _lib.MM_DENOISE_MAX_PASSES:
             raise ValueError(f"n_passes must be 1..{_lib.MM_DENOISE_MAX_PASSES}")
-        if out is None:
-            out = torch.empty(color.shape, dtype=torch.uint8 if rgba8 else torch.float32, device=color.device)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
-                  and out.dtype in (torch.float32, torch.uint8) and out.shape == color.shape
-                  and not (rgba8 and out.dtype != torch.uint8)):
-            raise ValueError("out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
+        out = self._filter_out(out, color.shape, color.device, rgba8,
+                               "out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
         r8 = out.dtype == torch.uint8
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
-        a = _lib.mm_aov(*[aov[k].data_ptr() for k in self.AOV_NAMES])
         p = _lib.mm_denoise_params(int(n_passes), float(sigma_z), float(sigma_l), _lib.MM_DN_RGBA8 if r8 else 0)
         self._check(lib().mm_denoise_frames(self._ctx, color.data_ptr(), C.byref(a), C.byref(p), n, w, h,
                                             out.data_ptr()))
@@ -366,10 +351,7 @@ class Renderer:
         this under that stream, as refine().)"""
         import torch
 
-        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
-                and color.dim() in (3, 4) and color.shape[-1] == 4):
-            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
-        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        n, h, w = self._frames(color)
         lead = tuple(color.shape[:-1])
         a = self._aov_frames(aov, n, h, w, color.device, "aov")
         if not (torch.is_tensor(var) and var.is_cuda and var.device == color.device and var.dtype == torch.float32
@@ -382,17 +364,11 @@ class Renderer:
             raise ValueError("count must be positive")
         if not 1 <= int(n_passes) <= _lib.MM_DENOISE_MAX_PASSES:
             raise ValueError(f"n_passes must be 1..{_lib.MM_DENOISE_MAX_PASSES}")
-        if out is None:
-            out = torch.empty(color.shape, dtype=torch.uint8 if rgba8 else torch.float32, device=color.device)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
-                  and out.dtype in (torch.float32, torch.uint8) and out.shape == color.shape
-                  and not (rgba8 and out.dtype != torch.uint8)):
-            raise ValueError("out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
-        if var_out is None:
-            var_out = torch.empty(var.shape, dtype=torch.float32, device=color.device) if return_var else None
-        elif not (torch.is_tensor(var_out) and var_out.is_cuda and var_out.device == color.device
-                  and var_out.is_contiguous() and var_out.dtype == torch.float32 and var_out.shape == var.shape):
-            raise ValueError("var_out must be a contiguous float32 CUDA tensor of var's shape")
+        out = self._filter_out(out, color.shape, color.device, rgba8,
+                               "out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
+        if var_out is not None or return_var:
+            var_out = self._filter_out(var_out, var.shape, color.device, None,
+                                       "var_out must be a contiguous float32 CUDA tensor of var's shape")
         r8 = out.dtype == torch.uint8
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
@@ -403,6 +379,74 @@ class Renderer:
                                                 C.byref(p), n, w, h, out.data_ptr(),
                                                 None if var_out is None else var_out.data_ptr()))
         return out if var_out is None else (out, var_out)
+
+    @staticmethod
+    def _frames(color):
+        """(n, h, w) of a colour tensor, (h, w, 4) or (n, h, w, 4)."""
+        import torch
+
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+                and color.dim() in (3, 4) and color.shape[-1] == 4):
+            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
+        return (1 if color.dim() == 3 else color.shape[0]), *color.shape[-3:-1]
+
+    _PLANE = "{what} must be a contiguous float32 tensor of shape {shape} on {device}"
+    _ENTRIES = "{what} must be a contiguous float32 {shape} tensor on {device}"  # (the pixel-list methods' wording)
+
+    @staticmethod
+    def _plane(t, what, shape, device, wording=_PLANE):
+        """`t`, a contiguous float32 tensor of `shape` on `device`."""
+        import torch
+
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == device and t.dtype == torch.float32
+                and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(wording.format(what=what, shape=shape, device=device))
+        return t
+
+    @staticmethod
+    def _filter_out(out, shape, device, rgba8, msg):
+        """A filter's output of `shape`: `out` if it fits (else ValueError(msg)), or a new tensor.  rgba8 None: float32;
+        else uint8 is allowed too, and it is what rgba8 asks for."""
+        import torch
+
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8 if rgba8 else torch.float32, device=device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == device and out.is_contiguous()
+                and out.dtype in ((torch.float32,) if rgba8 is None else (torch.float32, torch.uint8))
+                and out.shape == shape and not (rgba8 and out.dtype != torch.uint8)):
+            raise ValueError(msg)
+        return out
+
+    def _prev(self, prev, h, w, device, var):
+        """The mm_temporal_prev of accumulate()'s `prev` triple -- var: the mm_temporal_prev_var of accumulate_var()'s
+        quadruple -- for an h x w window on `device`."""
+        import torch
+
+        if var:
+            pc, pa, pcam, pvar = prev
+        else:
+            pc, pa, pcam = prev
+        if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == device and pc.dtype == torch.float32
+                and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
+            raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {device}")
+        if var:
+            if not (torch.is_tensor(pvar) and tuple(pvar.shape) in ((h, w), (1, h, w))):
+                raise ValueError(f"prev's variance must be a float32 tensor of shape {(h, w)} on {device}")
+            self._plane(pvar, "prev's variance", tuple(pvar.shape), device)
+        pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
+        fields = (pc.data_ptr(), self._aov_frames(pa, 1, h, w, device, "prev's aov"),
+                  _lib.mm_camera.from_buffer_copy(pcam.tobytes()))
+        return _lib.mm_temporal_prev_var(*fields, pvar.data_ptr()) if var else _lib.mm_temporal_prev(*fields)
+
+    @staticmethod
+    def _window(image):
+        """(h, w) of an accumulated frame, (h, w, 4)."""
+        import torch
+
+        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
+                and image.dim() == 3 and image.shape[-1] == 4):
+            raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
+        return tuple(image.shape[:2])
 
     def _aov_frames(self, aov, n, h, w, device, what):
         """The mm_aov of an aov dict whose buffers hold n frames of h x w on `device`."""
@@ -437,30 +481,16 @@ class Renderer:
         unchanged.  The inputs are not written."""
         import torch
 
-        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
-                and color.dim() in (3, 4) and color.shape[-1] == 4):
-            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
-        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        n, h, w = self._frames(color)
         cams = self._cameras(cameras)
         if cams.shape[0] != n:
             raise ValueError(f"{n} frames need {n} cameras, not {cams.shape[0]}")
         a = self._aov_frames(aov, n, h, w, color.device, "aov")
         if not 1 <= int(n_max) <= 65535:
             raise ValueError("n_max must be 1..65535")
-        if out is None:
-            out = torch.empty_like(color)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
-                  and out.dtype == torch.float32 and out.shape == color.shape):
-            raise ValueError("out must be a contiguous float32 CUDA tensor of color's shape")
-        pv = None
-        if prev is not None:
-            pc, pa, pcam = prev
-            if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == color.device and pc.dtype == torch.float32
-                    and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
-                raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {color.device}")
-            pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
-            pv = _lib.mm_temporal_prev(pc.data_ptr(), self._aov_frames(pa, 1, h, w, color.device, "prev's aov"),
-                                       _lib.mm_camera.from_buffer_copy(pcam.tobytes()))
+        out = self._filter_out(out, color.shape, color.device, None,
+                               "out must be a contiguous float32 CUDA tensor of color's shape")
+        pv = None if prev is None else self._prev(prev, h, w, color.device, False)
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
         p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
@@ -488,10 +518,7 @@ class Renderer:
         and select_noisy() with count 1.  The inputs are not written."""
         import torch
 
-        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
-                and color.dim() in (3, 4) and color.shape[-1] == 4):
-            raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
-        n, (h, w) = (1 if color.dim() == 3 else color.shape[0]), color.shape[-3:-1]
+        n, h, w = self._frames(color)
         lead = tuple(color.shape[:-1])
         cams = self._cameras(cameras)
         if cams.shape[0] != n:
@@ -499,37 +526,16 @@ class Renderer:
         a = self._aov_frames(aov, n, h, w, color.device, "aov")
         if not 1 <= int(n_max) <= 65535:
             raise ValueError("n_max must be 1..65535")
-
-        def plane(t, what, shape=lead):
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
-                    and t.is_contiguous() and tuple(t.shape) == shape):
-                raise ValueError(f"{what} must be a contiguous float32 tensor of shape {shape} on {color.device}")
-            return t
-
-        plane(vmean, "vmean")
+        self._plane(vmean, "vmean", lead, color.device)
         if weight is not None:
-            plane(weight, "weight")
-        if out is None:
-            out = torch.empty_like(color)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.device == color.device and out.is_contiguous()
-                  and out.dtype == torch.float32 and out.shape == color.shape):
-            raise ValueError("out must be a contiguous float32 CUDA tensor of color's shape")
+            self._plane(weight, "weight", lead, color.device)
+        out = self._filter_out(out, color.shape, color.device, None,
+                               "out must be a contiguous float32 CUDA tensor of color's shape")
         if var_out is None:
             var_out = torch.empty(lead, dtype=torch.float32, device=color.device)
         else:
-            plane(var_out, "var_out")
-        pv = None
-        if prev is not None:
-            pc, pa, pcam, pvar = prev
-            if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == color.device and pc.dtype == torch.float32
-                    and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
-                raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {color.device}")
-            if not (torch.is_tensor(pvar) and tuple(pvar.shape) in ((h, w), (1, h, w))):
-                raise ValueError(f"prev's variance must be a float32 tensor of shape {(h, w)} on {color.device}")
-            plane(pvar, "prev's variance", tuple(pvar.shape))
-            pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
-            pv = _lib.mm_temporal_prev_var(pc.data_ptr(), self._aov_frames(pa, 1, h, w, color.device, "prev's aov"),
-                                           _lib.mm_camera.from_buffer_copy(pcam.tobytes()), pvar.data_ptr())
+            self._plane(var_out, "var_out", lead, color.device)
+        pv = None if prev is None else self._prev(prev, h, w, color.device, True)
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
         p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
@@ -592,15 +598,10 @@ class Renderer:
         must not name a window pixel twice.  Returns `image`."""
         import torch
 
-        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
-                and image.dim() == 3 and image.shape[-1] == 4):
-            raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
+        h, w = self._window(image)
         pixels = self._pixel_list(pixels)
         n = pixels.shape[0]
-        if not (torch.is_tensor(extra) and extra.is_cuda and extra.device == image.device
-                and extra.dtype == torch.float32 and extra.is_contiguous() and tuple(extra.shape) == (n, 4)):
-            raise ValueError(f"extra must be a contiguous float32 ({n}, 4) tensor on {image.device}")
-        h, w = image.shape[:2]
+        self._plane(extra, "extra", (n, 4), image.device, self._ENTRIES)
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
         self._check(lib().mm_blend_pixels(self._ctx, image.data_ptr(), x0, y0, w, h, pixels.data_ptr() if n else None,
@@ -645,22 +646,12 @@ class Renderer:
         var)."""
         import torch
 
-        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
-                and image.dim() == 3 and image.shape[-1] == 4):
-            raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
-        h, w = image.shape[:2]
-        if not (torch.is_tensor(var) and var.is_cuda and var.device == image.device and var.dtype == torch.float32
-                and var.is_contiguous() and tuple(var.shape) == (h, w)):
-            raise ValueError(f"var must be a contiguous float32 ({h}, {w}) tensor on {image.device}")
+        h, w = self._window(image)
+        self._plane(var, "var", (h, w), image.device, self._ENTRIES)
         pixels = self._pixel_list(pixels)
         n = pixels.shape[0]
-        if not (torch.is_tensor(extra) and extra.is_cuda and extra.device == image.device
-                and extra.dtype == torch.float32 and extra.is_contiguous() and tuple(extra.shape) == (n, 4)):
-            raise ValueError(f"extra must be a contiguous float32 ({n}, 4) tensor on {image.device}")
-        if not (torch.is_tensor(extra_vmean) and extra_vmean.is_cuda and extra_vmean.device == image.device
-                and extra_vmean.dtype == torch.float32 and extra_vmean.is_contiguous()
-                and tuple(extra_vmean.shape) == (n,)):
-            raise ValueError(f"extra_vmean must be a contiguous float32 ({n},) tensor on {image.device}")
+        self._plane(extra, "extra", (n, 4), image.device, self._ENTRIES)
+        self._plane(extra_vmean, "extra_vmean", (n,), image.device, self._ENTRIES)
         if not self._pinned_stream:
             self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
         self._check(lib().mm_blend_pixels_var(self._ctx, image.data_ptr(), var.data_ptr(), x0, y0, w, h,

@@ -71,21 +71,9 @@ def test_symbol_exists_and_rejects_bad_arguments_without_a_gpu():
     assert call(o=col) == inv and call(o=var) == inv and call(vo=var) == inv and call(vo=col + 4) == inv
     assert call(vo=out + 8) == inv and call(vo=ids) == inv
     assert _lib.MM_DNV_RGBA8 == 1
-    # (a null context has no error text of its own: the messages are read with a context,
-    # tests/test_gpu_denoise_var.py)
-
-
-def test_rejections_are_this_call_s_not_the_null_context_s():
-    """With a null context every call returns MM_ERR_INVALID in the end, so the
-    test above cannot tell a check that is missing.  The library's source can:
-    each rejection the header lists has its own message under this call's name."""
-    src = (REPO / "mirror-maze_amd" / "csrc" / "mm_runtime.hip").read_text()
-    body = src[src.index("int mm_denoise_frames_var("):src.index("int mm_accumulate_frames(")]
-    assert body.index("if (!c) return MM_ERR_INVALID;") > body.rindex("return fail(c, MM_ERR_INVALID")
-    for what in ("null argument", "all three guide buffers", "n_passes must be", "unknown flags", "reserved must be 0",
-                 "eps_l must be positive and finite", "empty tile or no frames", "misaligned buffer",
-                 "more pixels than one call holds", "an output overlaps an input", "the two outputs overlap"):
-        assert f"mm_denoise_frames_var: {what}" in body, what
+    # (a null context has no error text of its own, and returns MM_ERR_INVALID whatever the checks do: that each
+    # rejection above is this call's own, with its message, and that the null context is refused after them, is
+    # tests/test_filter_args.py's; the messages with a context: tests/test_gpu_denoise_var.py)
 
 
 def test_params_layout_matches_the_header():
