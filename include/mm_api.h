@@ -499,6 +499,55 @@ int  mm_trace_pixels_var(mm_ctx* ctx, const mm_uniform* uni, const mm_ext* ext,
                          const uint32_t* pixels_dev, uint64_t n_pixels,
                          void* out_dev, float* var_dev, mm_stats* stats);
 
+/* ---- pixel lists of many frames in one launch -----------------------------------
+ * mm_trace_pixel_lists traces n_lists pixel lists, each with its own camera and
+ * RNG frame, in ONE launch (plus the resolve launch when the samples are
+ * staged): the refinement lists of a batch of frames, which have no dependency
+ * on each other, without one small launch per frame.
+ *
+ * pixels_dev: DEVICE pointer, 8-byte aligned, offsets[n_lists] pairs (x, y):
+ * the lists back to back; stream-ordered and not copied, as in mm_trace_pixels.
+ * offsets: HOST array of n_lists + 1 values, offsets[0] == 0, non-decreasing;
+ * list f is entries offsets[f] .. offsets[f+1] - 1 and may be empty.  cams:
+ * HOST array of n_lists cameras, or NULL for uni->cam on every list;
+ * frame_keys: HOST array of n_lists RNG frames, or NULL for ext->frame + f.
+ * The three host arrays are consumed on return.  out_dev: offsets[n_lists]
+ * float4 (or 4-byte pixels with MM_EXT_RGBA8); element e belongs to global
+ * entry e.
+ *
+ * var_dev == NULL: entry e of list f equals, on all bits, what mm_trace_pixels
+ * writes for it with uni->cam = cams[f] and ext->frame = frame_keys[f], under
+ * every rule of that call (entries outside the view, duplicates,
+ * MM_EXT_ACCUMULATE, MM_EXT_RGBA8, any spp in 1..4096; the resolve is fused
+ * or the samples staged by the same rule).  var_dev != NULL: offsets[n_lists]
+ * floats, 4-byte aligned, not overlapping out_dev; (out, var) are
+ * mm_trace_pixels_var's per entry, bit for bit, under that call's conditions
+ * (spp >= 2, no MM_EXT_ACCUMULATE, samples always staged).  stats: summed over
+ * the lists (rays and paths exact).
+ *
+ * A total of 0 entries: MM_OK, nothing enqueued, no call number taken.
+ * MM_ERR_INVALID: n_lists outside 1..65535; a null offsets, offsets[0] != 0 or
+ * a decreasing offset; with entries to trace, a null uni, ext, pixels_dev or
+ * out_dev, a misaligned pointer, MM_EXT_RGBA8 with MM_EXT_ACCUMULATE, spp or
+ * the limits out of range; the queue -- the sum over the lists of n_f * spp
+ * padded to 64, so that every list starts on a chunk boundary -- beyond the
+ * launch's 32-bit counter; more than 2^29 staged paths when the samples are
+ * staged.  MM_ERR_NO_SCENE without a scene; an earlier failed call is reported
+ * first.  MM_PIPE_WAVEFRONT: MM_ERR_UNSUPPORTED.  MM_PIPE_REFERENCE runs one
+ * reference list launch per non-empty list under the one call number (a
+ * baseline, not a rate).  Otherwise one wave-persistent launch, plus one
+ * resolve launch when the samples are staged (mm_last_timing counts 1 or 2);
+ * the launch never runs the mirror-tail rings (MM_INFO_LAST_DEFER reads 0).
+ * Numbered like the other trace calls; the call tracker names it
+ * mm_trace_pixel_lists with n_lists, the entries and spp.  The per-list records
+ * are context-owned and staged on the stream ahead of the launch, as
+ * mm_trace_tile_cameras stages cameras: back-to-back calls never share records
+ * and never wait on the host. */
+int  mm_trace_pixel_lists(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* cams,
+                          const mm_ext* ext, const uint32_t* frame_keys, uint32_t n_lists,
+                          const uint32_t* pixels_dev, const uint64_t* offsets,
+                          void* out_dev, float* var_dev, mm_stats* stats);
+
 /* ---- variance through the history ----------------------------------------------
  * mm_accumulate_frames with the variance of the pixel mean carried beside the
  * colour, and a weight per pixel and frame: the accumulated frame then has

@@ -67,6 +67,11 @@ struct mm_ctx {
     float* h_cams = nullptr;
     float* d_cams = nullptr;
     size_t cams_cap = 0, cams_next = 0;
+    // list tables of mm_trace_pixel_lists launches (mm_launch.h ListTable): the same arrangement, in 32-bit
+    // words (mm_runtime.hip stage_lists)
+    uint32_t* h_lists = nullptr;
+    uint32_t* d_lists = nullptr;
+    size_t lists_cap = 0, lists_next = 0;
     // mm_denoise_frames' scratch (mm_filters.hip dn_begin): the two intermediate images a frame's passes alternate between (one frame
     // each, `dn_img_cap` pixels in all) and the call's packed key records (`dn_keys_cap`).  A call's kernels are
     // ordered after the last call's on the same stream; `dn_done` (recorded after every call) orders them when

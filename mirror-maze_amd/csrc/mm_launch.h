@@ -49,6 +49,8 @@ struct TileJob {
     uint32_t fuse = 0;
     // 1: a pixel-list launch (mm_trace_pixels): `pixels` below names the pixels.  (In the padding ahead of
     // wave_ts: every other member keeps the offset it had without it.)
+    // 2: the pixel lists of several frames in one launch (mm_trace_pixel_lists): `lists` below is the launch's
+    // list table, which names the pixels.
     uint32_t list = 0;
     // Diagnostics (mm_set_wave_timeline): per wave of the wave-persistent
     // kernel, 4 x u64 = (entry, LDS staged, exit, chunks) in wall_clock64()
@@ -109,14 +111,37 @@ struct TileJob {
     // the kList instances only.  A launch has cameras or a list, never both, and the two pointers share the
     // slot: a member more would move the kernel arguments behind the job, and the camera-sequence instances'
     // register allocation with them (profiles/pixels/kernel_resources.txt).
+    //
+    // Pixel lists of several frames (mm_trace_pixel_lists, `list` == 2): the slot points at the launch's list
+    // table (ListTable below) -- the pixel array's address travels in its header, so the job needs no second
+    // pointer.  w = the entries of all lists together, h = 1; read by the kList == 2 instances only.
     union {
         const float* cams = nullptr;
         const uint2* pixels;
+        const uint32_t* lists;
     };
 };
 static_assert(sizeof(TileJob) == 224, "the kernel-argument layout the tile instances were measured with");
 constexpr uint32_t kCamStride = 16;
 static_assert(sizeof(mm_camera) <= kCamStride * sizeof(float), "a camera record holds an mm_camera");
+
+// The list table of an mm_trace_pixel_lists launch, an array of 32-bit words in device memory (written by a
+// copy that precedes the launch on its stream, by nothing while it runs; the kernel reads it with scalar loads):
+//   words 0..7                   header: the pixel array's address (low, high), n_lists, the queue's chunks, the
+//                                word offset of the records, 3 unused
+//   words 8..8 + n_lists         first chunk of every list, non-decreasing, and the queue's chunks once more:
+//                                chunk c belongs to the LAST list f with first[f] <= c (an empty list shares
+//                                its value with its successor; trailing empty lists hold the queue's chunks)
+//   words rec .. rec + 16 n      one 16-word record per list: the camera (10 floats), the RNG frame, the first
+//                                chunk, the chunks, the first global entry, the paths (entries * spp), the entries
+// rec is a multiple of 16 words, and so is the table's address: a record is one aligned 64-byte line.
+namespace ListTable {
+constexpr uint32_t kPixLo = 0, kPixHi = 1, kLists = 2, kChunks = 3, kRecords = 4, kHeader = 8, kRecWords = 16;
+constexpr uint32_t kKey = 10, kFirstChunk = 11, kNumChunks = 12, kFirstEntry = 13, kPaths = 14, kEntries = 15;
+constexpr uint32_t records_at(uint32_t n_lists) { return (kHeader + n_lists + 1u + 15u) & ~15u; }
+constexpr size_t words(uint32_t n_lists) { return (size_t)records_at(n_lists) + (size_t)kRecWords * n_lists; }
+}  // namespace ListTable
+static_assert(sizeof(mm_camera) <= ListTable::kKey * sizeof(float), "a list record's camera words hold an mm_camera");
 
 // (Error flag bits kErr* and kStatusDone: mm_calls.h.)
 // One-thread kernel that publishes a non-persistent launch's error flag into

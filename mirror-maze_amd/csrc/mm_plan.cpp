@@ -217,4 +217,60 @@ LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels)
     return p;
 }
 
+int lists_total(const uint64_t* offsets, uint32_t n_lists, uint64_t& total, std::string& error) {
+    total = 0;
+    error.clear();
+    if (n_lists == 0 || n_lists > 65535u) error = "mm_trace_pixel_lists: n_lists outside 1..65535";
+    else if (!offsets) error = "mm_trace_pixel_lists: null offsets";
+    else if (offsets[0] != 0) error = "mm_trace_pixel_lists: offsets[0] is not 0";
+    else
+        for (uint32_t f = 0; f < n_lists && error.empty(); ++f)
+            if (offsets[f + 1] < offsets[f]) error = "mm_trace_pixel_lists: offsets decrease";
+    if (!error.empty()) return MM_ERR_INVALID;
+    total = offsets[n_lists];
+    return MM_OK;
+}
+
+ListsPlan plan_pixel_lists(const PlanOptions& o, const mm_ext& e, const uint64_t* offsets, uint32_t n_lists) {
+    ListsPlan r;
+    auto refuse_with = [&](int code, const std::string& why) {
+        r.plan.code = code;
+        r.plan.error = why;
+        r.lists.clear();
+        return r;
+    };
+    if (o.pipe == MM_PIPE_WAVEFRONT)
+        return refuse_with(MM_ERR_UNSUPPORTED, "mm_trace_pixel_lists: MM_PIPE_WAVEFRONT runs the tail rings, which a "
+                                               "pixel list never does");
+    std::string why;
+    if (int rc = lists_total(offsets, n_lists, r.n_entries, why)) return refuse_with(rc, why);
+    const char* too_many = "mm_trace_pixel_lists: more paths than one launch holds (2^32)";
+    // (n_entries < 2^63 / 4096 first: no product below can wrap)
+    if (r.n_entries > 0xFFFFFFFFull || e.spp == 0) return refuse_with(MM_ERR_INVALID, too_many);
+    const bool persist = o.pipe != MM_PIPE_REFERENCE && o.opt_persist == 2;
+    uint64_t chunks = 0;  // at most 2^32 * 4096 / 64 + 65535
+    r.lists.resize(n_lists);
+    for (uint32_t f = 0; f < n_lists; ++f) {
+        const uint64_t n = offsets[f + 1] - offsets[f], paths = n * e.spp;
+        ListSpan& l = r.lists[f];
+        // (values past 32 bits are refused below, before anything reads the spans)
+        l.first_chunk = (uint32_t)chunks;
+        l.n_chunks = (uint32_t)((paths + 63) / 64);
+        l.first_entry = (uint32_t)offsets[f];
+        l.n_entries = (uint32_t)n;
+        l.n_paths = (uint32_t)paths;
+        chunks += (paths + 63) / 64;
+    }
+    if (chunks * 64 + (1ull << 24) > 0xFFFFFFFFull) return refuse_with(MM_ERR_INVALID, too_many);
+    r.n_chunks = (uint32_t)chunks;
+    r.plan.predraw = plan_predraw(o.opt_predraw, o.opt_predraw_pool, e.bounce_limit);
+    r.plan.predraw_pool = plan_predraw_pool(o.opt_predraw_pool, e.bounce_limit);
+    r.plan.fuse = persist && o.opt_fuse && 64 % e.spp == 0;
+    r.plan.rows_per_batch = 1;
+    if (!r.plan.fuse && r.n_entries * e.spp > kStagePathsMax)
+        return refuse_with(MM_ERR_INVALID, "mm_trace_pixel_lists: the lists' staged samples exceed 6 GiB (2^29 paths); "
+                                           "use shorter lists");
+    return r;
+}
+
 }  // namespace mm

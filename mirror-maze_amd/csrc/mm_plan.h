@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "mm_api.h"
 #include "mm_variants.h"
@@ -89,5 +90,38 @@ LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mo
 // spp in chunks padded to 64, beyond the 32-bit counter (less the 2^24 the waves' last claims may overshoot),
 // or staged samples beyond kStagePathsMax.  rows_per_batch is 1.
 LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels);
+
+// The pixel lists of several frames in ONE launch (mm_trace_pixel_lists): list f is entries offsets[f] ..
+// offsets[f + 1] - 1 of the concatenated pixel array.  Each list's paths, entries * spp, are padded to whole
+// 64-path chunks, so every list starts on a chunk boundary and a chunk belongs to one list.
+struct ListSpan {
+    uint32_t first_chunk = 0, n_chunks = 0;  // of the launch's queue
+    uint32_t first_entry = 0, n_entries = 0;  // of the concatenation (offsets[f], offsets[f + 1] - offsets[f])
+    uint32_t n_paths = 0;                     // n_entries * spp
+};
+struct ListsPlan {
+    LaunchPlan plan;              // fuse-or-stage by plan_pixels' rule; code / error as there
+    uint64_t n_entries = 0;       // offsets[n_lists]
+    uint32_t n_chunks = 0;        // the queue, in chunks
+    std::vector<ListSpan> lists;  // n_lists spans (an empty list: n_chunks 0, its successor's first_chunk)
+};
+// The entries of all lists, offsets[n_lists], or the refusal: a null `offsets`, n_lists outside 1..65535,
+// offsets[0] != 0, or a decreasing offset (code MM_ERR_INVALID and the text in `error`).
+int lists_total(const uint64_t* offsets, uint32_t n_lists, uint64_t& total, std::string& error);
+// MM_ERR_INVALID: lists_total's refusals; the queue -- the sum of the lists' padded paths -- beyond the 32-bit
+// counter (less the 2^24 the waves' last claims may overshoot); staged samples beyond kStagePathsMax.
+// MM_ERR_UNSUPPORTED: MM_PIPE_WAVEFRONT.  A total of 0 entries is a valid plan with no chunks.
+ListsPlan plan_pixel_lists(const PlanOptions& o, const mm_ext& e, const uint64_t* offsets, uint32_t n_lists);
+// The list chunk `chunk` (< the queue's chunks) belongs to, by the search the kernel runs over the table of
+// first chunks (first[0 .. n_lists], first[n_lists] = the queue's chunks): the last f with first[f] <= chunk.
+inline uint32_t list_of_chunk(const uint32_t* first, uint32_t n_lists, uint32_t chunk) {
+    uint32_t lo = 0, hi = n_lists;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= chunk) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
 
 }  // namespace mm

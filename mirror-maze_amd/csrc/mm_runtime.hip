@@ -173,6 +173,37 @@ int stage_cameras(mm_ctx* c, const mm_camera* cams, uint32_t n, const float*& de
     return MM_OK;
 }
 
+// The list table of an mm_trace_pixel_lists launch (mm_launch.h ListTable), staged as stage_cameras stages
+// camera records: `words` words (a multiple of 16, so every table starts on a 64-byte line) of a pinned ring
+// that `fill` writes, mirrored to the device by a copy on the context's stream ahead of the launch.  Every
+// call takes fresh words; nothing waits for the GPU unless the ring is full (then once, and the ring grows up
+// to kListsWrap words, from where on it wraps).
+constexpr size_t kListsMin = 1024, kListsWrap = 1u << 22;
+template <typename F>
+int stage_lists(mm_ctx* c, size_t words, F&& fill, const uint32_t*& dev) {
+    if (c->lists_next + words > c->lists_cap) {
+        HIPC(c, hipDeviceSynchronize());  // staged tables may still be on their way, on any stream used so far
+        if (words > c->lists_cap || c->lists_cap < kListsWrap) {
+            const size_t cap = std::max<size_t>({kListsMin, 2 * c->lists_cap, words});
+            if (c->h_lists) (void)hipHostFree(c->h_lists);
+            (void)hipFree(c->d_lists);
+            c->h_lists = nullptr; c->d_lists = nullptr; c->lists_cap = 0;
+            HIPC(c, hipHostMalloc((void**)&c->h_lists, cap * sizeof(uint32_t), hipHostMallocDefault));
+            HIPC(c, hipMalloc((void**)&c->d_lists, cap * sizeof(uint32_t)));
+            c->lists_cap = cap;
+        }
+        c->lists_next = 0;
+    }
+    uint32_t* h = c->h_lists + c->lists_next;
+    std::memset(h, 0, words * sizeof(uint32_t));
+    fill(h);
+    uint32_t* d = c->d_lists + c->lists_next;
+    HIPC(c, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    c->lists_next += words;
+    dev = d;
+    return MM_OK;
+}
+
 int begin_timing(mm_ctx* c) {
     HIPC(c, hipEventRecord(c->ev0, c->stream));
     return MM_OK;
@@ -324,6 +355,8 @@ void mm_destroy(mm_ctx* c) {
     (void)hipFree(c->d_gather);
     (void)hipFree(c->d_cams);
     if (c->h_cams) (void)hipHostFree(c->h_cams);
+    (void)hipFree(c->d_lists);
+    if (c->h_lists) (void)hipHostFree(c->h_lists);
     (void)hipFree(c->d_dn_img); (void)hipFree(c->d_dn_keys); (void)hipFree(c->d_dn_var);
     if (c->dn_done) (void)hipEventDestroy(c->dn_done);
     if (c->gather_done) (void)hipEventDestroy(c->gather_done);
@@ -998,6 +1031,173 @@ int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint3
 int mm_trace_pixels_var(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
                         void* out_dev, float* var_dev, mm_stats* stats) {
     return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, true, var_dev);
+}
+
+// The pixel lists of several frames in one launch: mm_trace_pixels' checks in its order, the plan
+// (mm_plan.h plan_pixel_lists), the list table staged ahead of the launch, one kList == 2 launch and, with
+// staged samples, one resolve over the concatenation as ONE list (its slots are global entry * spp + sample).
+// MM_PIPE_REFERENCE: one unchanged k_trace_mega list launch per non-empty list, each into its own slice of
+// the staged samples, and the same resolve.  var_dev: the variance call (mm_trace_pixels_var's conditions).
+int mm_trace_pixel_lists(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e,
+                         const uint32_t* frame_keys, uint32_t n_lists, const uint32_t* pixels_dev,
+                         const uint64_t* offsets, void* out_dev, float* var_dev, mm_stats* stats) {
+    if (!c) return MM_ERR_INVALID;
+    const char* fn = "mm_trace_pixel_lists";
+    const bool var_call = var_dev != nullptr;
+    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
+    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_pixel_lists: no scene uploaded");
+    uint64_t n_entries = 0;
+    std::string why;
+    if (int rc0 = lists_total(offsets, n_lists, n_entries, why)) return fail(c, rc0, why);
+    if (n_entries == 0) return MM_OK;
+    if (!u || !e || !pixels_dev || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: null argument");
+    if (int rc0 = check_tile(c, fn, u, e, e->mirror_limit, 0, 0, 1, 1, 1)) return rc0;
+    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
+    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
+        return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: MM_EXT_RGBA8 results cannot accumulate");
+    const size_t out_bpp = rgba8 ? 4 : 16;
+    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
+        return fail(c, MM_ERR_INVALID, std::string("mm_trace_pixel_lists: lists not 8-byte or output not ") +
+                                           std::to_string(out_bpp) + "-byte aligned");
+    if (var_call) {
+        if (n_entries > 0xFFFFFFFFull)  // (the plan's own refusal, ahead of the byte counts below)
+            return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: more paths than one launch holds (2^32)");
+        if (int rc0 = check_var(c, fn, e, out_dev, n_entries * out_bpp, var_dev, n_entries)) return rc0;
+    }
+    HIPC(c, hipSetDevice(c->device));
+    const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
+    const bool persist = c->pipe != MM_PIPE_REFERENCE && c->opt_persist == 2;
+    const SceneFacts facts = scene_facts(c);
+    PlanOptions opts = plan_options(c);
+    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
+    const ListsPlan lp = plan_pixel_lists(opts, *e, offsets, n_lists);
+    if (lp.plan.code != MM_OK) return fail(c, lp.plan.code, lp.plan.error);
+    int form = 0, mode = 0;
+    if (persist) {
+        Choice m = choose_method(facts, opts);
+        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
+        if (m.code != MM_OK) return fail(c, m.code, m.error);
+        form = m.form;
+        mode = m.mode;
+    }
+    const bool fuse = lp.plan.fuse;
+    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e->spp));
+    if (rc) return rc;
+    auto key_of = [&](uint32_t f) { return frame_keys ? frame_keys[f] : e->frame + f; };
+    auto cam_of = [&](uint32_t f) -> const mm_camera& { return cams ? cams[f] : u->cam; };
+    const uint32_t* table_dev = nullptr;
+    if (persist) {
+        rc = stage_lists(c, ListTable::words(n_lists), [&](uint32_t* t) {
+            const uintptr_t px = reinterpret_cast<uintptr_t>(pixels_dev);
+            t[ListTable::kPixLo] = (uint32_t)px;
+            t[ListTable::kPixHi] = (uint32_t)((uint64_t)px >> 32);
+            t[ListTable::kLists] = n_lists;
+            t[ListTable::kChunks] = lp.n_chunks;
+            t[ListTable::kRecords] = ListTable::records_at(n_lists);
+            for (uint32_t f = 0; f < n_lists; ++f) {
+                const ListSpan& l = lp.lists[f];
+                t[ListTable::kHeader + f] = l.first_chunk;
+                uint32_t* r = t + ListTable::records_at(n_lists) + (size_t)f * ListTable::kRecWords;
+                std::memcpy(r, &cam_of(f), sizeof(mm_camera));
+                r[ListTable::kKey] = key_of(f);
+                r[ListTable::kFirstChunk] = l.first_chunk;
+                r[ListTable::kNumChunks] = l.n_chunks;
+                r[ListTable::kFirstEntry] = l.first_entry;
+                r[ListTable::kPaths] = l.n_paths;
+                r[ListTable::kEntries] = l.n_entries;
+            }
+            t[ListTable::kHeader + n_lists] = lp.n_chunks;
+        }, table_dev);
+        if (rc) return rc;
+    }
+    if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
+    if ((rc = begin_timing(c))) return rc;
+    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
+    const DevScene sc = dev_scene(c);
+    // the concatenation as one list: the resolve's job, and the base of the launches'
+    TileJob all;
+    all.u = *u;
+    all.e = *e;
+    all.x0 = 0;
+    all.y0 = 0;
+    all.w = (uint32_t)n_entries;
+    all.h = 1;
+    all.y_stride = 1;
+    all.view_w = (uint32_t)u->view_w;
+    all.fuse = fuse ? 1u : 0u;
+    all.wave_ts = c->d_wave_ts;
+    all.wave_ts_cap = c->wave_ts_cap;
+    all.out = out_dev;
+    all.reserve_cus = c->opt_reserve_cus;
+    all.predraw = lp.plan.predraw;
+    all.predraw_pool = lp.plan.predraw_pool;
+    all.fault = c->opt_fault == 1 ? 1u : 0u;
+    all.ring_diag = c->d_status + kStatusSlots;
+    all.list = 1;
+    all.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+    c->calls.begin_call();
+    uint32_t launches = 0;
+    if (persist) {
+        TileJob job = all;
+        job.list = 2;
+        job.lists = table_dev;
+        rc = enqueue_launch(c, true, [&](uint32_t* status, uint32_t launch_id) -> int {
+            job.status = status;
+            job.launch_id = launch_id;
+            if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
+            c->last_form = form >= kFormGrid ? kFormGrid : form;
+            c->last_mode = mode;
+            c->last_kern_mode = mode;
+            c->last_kern_form = form;
+            c->last_kern_ring = 0;
+            HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev, c->d_work, want_stats, mode,
+                                             form, c->stream));
+            return MM_OK;
+        });
+        if (!rc) ++launches;
+    } else {
+        for (uint32_t f = 0; f < n_lists && !rc; ++f) {
+            const ListSpan& l = lp.lists[f];
+            if (!l.n_entries) continue;
+            TileJob job = all;
+            job.u.cam = cam_of(f);
+            job.e.frame = key_of(f);
+            job.w = l.n_entries;
+            job.pixels = all.pixels + l.first_entry;
+            job.out = reinterpret_cast<char*>(out_dev) + (size_t)l.first_entry * out_bpp;
+            Sample* samples = c->d_samples + (size_t)l.first_entry * e->spp;
+            rc = enqueue_launch(c, false, [&](uint32_t* status, uint32_t launch_id) -> int {
+                job.status = status;
+                job.launch_id = launch_id;
+                if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
+                MegaOpts mo;
+                mo.reference = true;
+                mo.block = c->opt_block ? c->opt_block : 256u;
+                HIPC(c, launch_trace_mega(sc, job, samples, c->d_aux, err_dev, want_stats, mo, c->stream));
+                return MM_OK;
+            });
+            if (!rc) ++launches;
+        }
+    }
+    if (!rc && !fuse) {
+        const hipError_t re = var_call ? launch_resolve_var(all, c->d_samples, out_dev, var_dev, c->stream)
+                                       : launch_resolve(all, c->d_samples, out_dev, c->stream);
+        if (re != hipSuccess) rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
+        ++launches;
+    }
+    c->last_defer = false;
+    char what[160] = "";
+    if (c->calls.call_has_launches())
+        snprintf(what, sizeof(what), "%s, %u lists, %llu pixels, %u spp", fn, n_lists, (unsigned long long)n_entries,
+                 e->spp);
+    c->calls.end_call(what);
+    if (rc) return rc;
+    if ((rc = end_timing(c, launches))) return rc;
+    if (want_stats) {
+        if ((rc = read_aux(c, stats))) return rc;
+        return report_failure(c, "");
+    }
+    return MM_OK;
 }
 
 namespace {

@@ -69,6 +69,16 @@ __device__ __forceinline__ bool list_pixel(const TileJob& job, uint32_t pix, uin
     return r.x < job.view_w && r.y < (uint32_t)job.u.view_h;
 }
 
+// The same for global entry `e` of an mm_trace_pixel_lists launch, whose pixel array's address comes from the
+// list table's header (job.lists), not from the job.
+__device__ __forceinline__ bool list_pixel_at(const uint2* __restrict__ pixels, const TileJob& job, size_t e,
+                                              uint32_t& px, uint32_t& py) {
+    const uint2 r = pixels[e];
+    px = r.x;
+    py = r.y;
+    return r.x < job.view_w && r.y < (uint32_t)job.u.view_h;
+}
+
 // The pixel's mean, sum / spp: when spp = 2^k as sum * 2^-k (both are the
 // exact sum x 2^-k rounded once: the same float, without three IEEE divisions).
 __device__ __forceinline__ F3 pixel_mean(F3 acc, uint32_t spp) {

@@ -477,20 +477,81 @@ __device__ __forceinline__ mm_uniform chunk_uniform(const TileJob& job, uint32_t
     return u;
 }
 
+// Pixel lists of several frames in one launch (kList == 2, mm_trace_pixel_lists; mm_launch.h ListTable).  Every
+// list's paths are padded to whole chunks, so a chunk belongs to one list: the last list whose first chunk is
+// at most the chunk's index (empty lists share their first chunk with their successor and are stepped over).
+// The table's address is a kernel argument and the chunk index comes from a readfirstlane'd queue index, so the
+// search is wave-uniform; read through the constant address space its loads are scalar, as chunk_uniform's.
+typedef const uint32_t __attribute__((address_space(4))) list_word;
+struct ListCursor {  // the list the wave's last chunk belonged to: a claim's next chunk is usually its neighbour
+    uint32_t f = 0, first_chunk = 0, n_chunks = 0;  // (n_chunks 0: no list yet)
+    uint32_t first_entry = 0, n_paths = 0, key = 0;
+};
+__device__ __forceinline__ uint32_t list_of_chunk(list_word* t, uint32_t n_lists, uint32_t qc) {
+    list_word* first = t + ListTable::kHeader;
+    uint32_t lo = 0, hi = n_lists;  // first[lo] <= qc < first[hi]: first[0] = 0, first[n_lists] = the queue's chunks
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= qc) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ void list_seek(const TileJob& job, uint32_t qc, ListCursor& lc) {
+    if (qc - lc.first_chunk < lc.n_chunks) return;  // (unsigned: also false below the cursor's first chunk)
+    list_word* t = (list_word*)job.lists;
+    const uint32_t f = list_of_chunk(t, t[ListTable::kLists], qc);
+    list_word* r = t + t[ListTable::kRecords] + f * ListTable::kRecWords;
+    lc.f = f;
+    lc.key = r[ListTable::kKey];
+    lc.first_chunk = r[ListTable::kFirstChunk];
+    lc.n_chunks = r[ListTable::kNumChunks];
+    lc.first_entry = r[ListTable::kFirstEntry];
+    lc.n_paths = r[ListTable::kPaths];
+}
+// The uniform list f's chunks are traced with: chunk_uniform's loads, from the list's record.
+__device__ __forceinline__ mm_uniform list_uniform(const TileJob& job, uint32_t f) {
+    mm_uniform u = job.u;
+    typedef const float __attribute__((address_space(4))) cam_float;
+    list_word* t = (list_word*)job.lists;
+    cam_float* r = (cam_float*)(t + t[ListTable::kRecords] + f * ListTable::kRecWords);
+    u.cam.center[0] = r[0]; u.cam.center[1] = r[1]; u.cam.center[2] = r[2];
+    u.cam.focal = r[3];
+    u.cam.quat[0] = r[4]; u.cam.quat[1] = r[5]; u.cam.quat[2] = r[6]; u.cam.quat[3] = r[7];
+    u.cam.viewport[0] = r[8]; u.cam.viewport[1] = r[9];
+    return u;
+}
+__device__ __forceinline__ const uint2* list_pixels(const TileJob& job) {
+    list_word* t = (list_word*)job.lists;
+    return reinterpret_cast<const uint2*>((uintptr_t)t[ListTable::kPixLo] | ((uintptr_t)t[ListTable::kPixHi] << 32));
+}
+
 // Pixel-list launches (kList, mm_trace_pixels; w = n_pixels, h = 1, one frame): the pixel of queue slot
 // `path` is record path / spp of job.pixels instead of the tile's (x0 + i, y0 + j * y_stride) -- 8 B per lane,
 // spp consecutive lanes the same record, a chunk's 64 lanes at most 64 consecutive records --, consumed into
 // p.sb and p.dir before the bounce loop like the tile's.  A lane whose entry lies outside the view is not
 // valid: it runs nothing and counts nothing, and with the fused resolve its pixel's first lane writes the
 // entry's zero before the chunk's bounces (staged samples: the resolve kernel does).
-template <bool kStats, bool kCams, bool kList, typename Q>
+//
+// Lists of several frames (kList == 2, mm_trace_pixel_lists): the queue holds every list's chunks back to back;
+// a chunk's list comes from list_seek, its local path index is (chunk - the list's first chunk) * 64 + lane,
+// valid below the list's paths, and its entry is the list's first global entry + path / spp -- out, the staged
+// samples (slot entry * spp + sample) and store_unlisted are indexed by that global entry.  The camera and the
+// RNG frame are the list's.  With 64 % spp == 0 a pixel's samples never straddle a chunk, as in a single list.
+template <bool kStats, bool kCams, int kList, typename Q>
 __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q& q, const TileJob& job,
                                                      Sample* __restrict__ samples, unsigned long long* stats,
                                                      uint32_t* err, uint32_t* work) {
     const uint32_t spp = job.e.spp;
     const uint32_t n_paths = job.w * job.h * spp;         // per frame
     const uint32_t cpf = (n_paths + 63u) / 64u;           // 64-path chunks per frame
-    const uint32_t n_queue = cpf * 64u * job.n_frames;    // the queue, in paths (chunks padded to 64)
+    uint32_t n_queue = cpf * 64u * job.n_frames;          // the queue, in paths (chunks padded to 64)
+    ListCursor lc;
+    const uint2* lpix = nullptr;
+    if constexpr (kList == 2) {
+        n_queue = ((list_word*)job.lists)[ListTable::kChunks] * 64u;
+        lpix = list_pixels(job);
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const F3 ori = F3{job.u.cam.center[0], job.u.cam.center[1], job.u.cam.center[2]};
     Counters c;
@@ -506,15 +567,23 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
         ++chunks;
         mark_chunk_start(job, 0u);
         const uint32_t qc = base >> 6;
-        const uint32_t fr = job.n_frames > 1 ? qc / cpf : 0u;
-        const uint32_t path = (qc - fr * cpf) * 64u + lane;
-        bool valid = path < n_paths;
+        if constexpr (kList == 2) list_seek(job, qc, lc);
+        const uint32_t fr = kList == 2 ? 0u : job.n_frames > 1 ? qc / cpf : 0u;
+        const uint32_t path = kList == 2 ? (qc - lc.first_chunk) * 64u + lane : (qc - fr * cpf) * 64u + lane;
+        bool valid = kList == 2 ? path < lc.n_paths : path < n_paths;
         uint32_t lx = 0, ly = 0;
-        if constexpr (kList) {
+        if constexpr (kList == 1) {
             if (valid) {
                 const uint32_t e = path / spp;
                 valid = list_pixel(job, e, lx, ly);
                 if (!valid && job.fuse && path == e * spp) store_unlisted(job, job.out, e);
+            }
+        }
+        if constexpr (kList == 2) {
+            if (valid) {
+                const uint32_t e = path / spp;
+                valid = list_pixel_at(lpix, job, (size_t)lc.first_entry + e, lx, ly);
+                if (!valid && job.fuse && path == e * spp) store_unlisted(job, job.out, (size_t)lc.first_entry + e);
             }
         }
         F3 s = F3{0.0f, 0.0f, 0.0f};
@@ -523,8 +592,12 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             const uint32_t j = pix / job.w, i = pix - j * job.w;
             const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
             PathState p;
-            p.sb = seed_tile(py * job.view_w + px, smp, job.e.frame + fr);
-            if constexpr (kCams) {  // ori is not loop-invariant in a camera sequence
+            p.sb = seed_tile(py * job.view_w + px, smp, kList == 2 ? lc.key : job.e.frame + fr);
+            if constexpr (kList == 2) {  // the list's camera, per chunk as a camera sequence's
+                const mm_uniform cu = list_uniform(job, lc.f);
+                p.dir = jitter(primary_dir(cu, px, py), p.sb);
+                p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
+            } else if constexpr (kCams) {  // ori is not loop-invariant in a camera sequence
                 const mm_uniform cu = chunk_uniform(job, fr);
                 p.dir = jitter(primary_dir(cu, px, py), p.sb);
                 p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
@@ -541,10 +614,18 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             bounce_loop<kStats>(sc, q, p, (int)job.e.bounce_limit, (int)job.e.mirror_limit, stack, c, overflow);
             if (overflow) atomicOr(err, kErrStack);
             s = path_value(p);
-            if (!job.fuse) samples[fr * n_paths + path] = s;
+            if constexpr (kList == 2) {
+                if (!job.fuse) samples[((size_t)lc.first_entry + pix) * spp + smp] = s;
+            } else {
+                if (!job.fuse) samples[fr * n_paths + path] = s;
+            }
             paths++;
         }
-        if (job.fuse) resolve_in_wave(job, s, path, valid, job.out, (size_t)fr * job.w * job.h);
+        if constexpr (kList == 2) {
+            if (job.fuse) resolve_in_wave(job, s, path, valid, job.out, (size_t)lc.first_entry);
+        } else {
+            if (job.fuse) resolve_in_wave(job, s, path, valid, job.out, (size_t)fr * job.w * job.h);
+        }
     }
 #ifdef MM_PHASE_CLOCKS
     {  // the wave's time in queries / shading: the max over its lanes (some lane runs every iteration)
@@ -923,7 +1004,8 @@ constexpr uint32_t kWpThreads = MM_WP_THREADS;
 // the feature (gate: profiles/camera_sequence/kernel_resources.txt).
 // kList: a pixel-list launch (job.pixels, mm_trace_pixels), built for kRing = 0 and kCams = false only; the
 // tile instances' code is the same with and without the feature (gate: profiles/pixels/kernel_resources.txt).
-template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false, bool kList = false>
+// kList == 2: the pixel lists of several frames (job.lists, mm_trace_pixel_lists), under kList == 1's conditions.
+template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false, int kList = 0>
 __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersist(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                                unsigned long long* stats, uint32_t* err,
                                                                uint32_t* work) {
@@ -987,8 +1069,12 @@ static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, S
     if (job.list) {  // a pixel list: the plain body's instances, one frame
         if constexpr (kRing == 0) {
             if (job.n_frames != 1) return hipErrorInvalidValue;
-            kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, true>
-                               : k_trace_wavepersist<false, kLds, kForm, 0, false, true>;
+            if (job.list == 2)
+                kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, 2>
+                                   : k_trace_wavepersist<false, kLds, kForm, 0, false, 2>;
+            else
+                kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, 1>
+                                   : k_trace_wavepersist<false, kLds, kForm, 0, false, 1>;
         } else {
             return hipErrorInvalidValue;
         }

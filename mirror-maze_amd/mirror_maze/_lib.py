@@ -167,6 +167,8 @@ EXPORTS = {
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, C.POINTER(mm_stats)]),
     "mm_trace_pixels_var": (C.c_int, [P, C.POINTER(mm_uniform), C.POINTER(mm_ext), P, C.c_uint64, P, P,
                                       C.POINTER(mm_stats)]),
+    "mm_trace_pixel_lists": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), P, C.c_uint32, P, P, P, P,
+                                       C.POINTER(mm_stats)]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

@@ -794,6 +794,84 @@ class Renderer:
         count[j, i] = cnt
         return n
 
+    # -- pixel lists of many frames in one launch -----------------------------------
+    def trace_pixel_lists(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, pixels, offsets,
+                          frame_keys=None, out=None, var=None, stats: bool = False, rgba8: bool = False):
+        """The pixel lists of several frames in ONE launch
+        (mm_trace_pixel_lists).  `pixels`: the lists back to back, as
+        trace_pixels takes one; `offsets`: n_lists + 1 integers on the host,
+        offsets[0] = 0 and non-decreasing -- list f is pixels[offsets[f] :
+        offsets[f + 1]] and may be empty.  `cameras`: what trace_tile_cameras
+        takes, one per list, or None for uniform.cam on every list;
+        `frame_keys`: the lists' RNG frames, or None for ext.frame + f.  Entry
+        e of the (n, 4) result equals trace_pixels' for it with its list's
+        camera and frame, bit for bit.  `var`: None for the plain call, True
+        or an (n,) float32 CUDA tensor for the variance call, whose (out, var)
+        are trace_pixels_var's.  Returns (out, var or None, mm_stats or
+        None)."""
+        import torch
+
+        pixels = self._pixel_list(pixels)
+        offs = np.ascontiguousarray(np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets),
+                                    dtype=np.uint64).reshape(-1)
+        n_lists = offs.shape[0] - 1
+        if n_lists < 1:
+            raise ValueError("offsets must hold n_lists + 1 values, n_lists >= 1")
+        n = pixels.shape[0]
+        if int(offs[-1]) != n:
+            raise ValueError(f"offsets end at {int(offs[-1])}, the pixel array holds {n} entries")
+        cams = None if cameras is None else self._cameras(cameras)
+        if cams is not None and cams.shape[0] != n_lists:
+            raise ValueError(f"{n_lists} lists need {n_lists} cameras, not {cams.shape[0]}")
+        keys = None
+        if frame_keys is not None:
+            keys = np.ascontiguousarray(np.asarray(frame_keys), dtype=np.uint32).reshape(-1)
+            if keys.shape[0] != n_lists:
+                raise ValueError(f"{n_lists} lists need {n_lists} frame keys, not {keys.shape[0]}")
+        out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
+        if var is True:
+            var = torch.zeros((n,), dtype=torch.float32, device=pixels.device)
+        if var is not None and not (torch.is_tensor(var) and var.is_cuda and var.dtype == torch.float32
+                                    and var.is_contiguous() and tuple(var.shape) == (n,)):
+            raise ValueError(f"var must be None, True or a contiguous float32 CUDA tensor of {n} elements")
+        if not self._pinned_stream:
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
+        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
+        st = _lib.mm_stats()
+        self._check(lib().mm_trace_pixel_lists(
+            self._ctx, C.byref(uniform), None if cams is None else cams.ctypes.data, C.byref(e),
+            None if keys is None else keys.ctypes.data, n_lists, pixels.data_ptr() if n else None, offs.ctypes.data,
+            out.data_ptr() if n else None, var.data_ptr() if var is not None and n else None, C.byref(st)))
+        return out, var, (st if stats else None)
+
+    def refine_frames(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, color, var, count, rel_tol: float,
+                      extra_spp: int, frame_keys, ids=None, x0: int = 0, y0: int = 0):
+        """One round of refine() for a whole batch of frames, in place, with one
+        selection, one trace launch and one merge for all of them.  `color` (n,
+        h, w, 4), `var` and `count` (n, h, w) float32 CUDA tensors: the window
+        (x0, y0, w, h) of n frames as trace_tile_var(cameras=...) returned
+        them, frame f traced with cameras[f]; `frame_keys`: n RNG frames, one
+        per frame, new for every round (refine()'s rule); `ids`: the guides' id
+        buffers, (n, h, w).  The result equals refine() called per frame with
+        uniform.cam = cameras[f] and frame_keys[f], on all bits of colour,
+        variance and count.  Returns the selected pixels per frame, a list of n
+        ints; nothing is launched when no frame selects any."""
+        pixels, offsets, fji = _select_noisy_frames(color, var, count, rel_tol, 1e-3, ids, x0, y0)
+        counts = [int(b - a) for a, b in zip(offsets[:-1], offsets[1:])]
+        if int(offsets[-1]) == 0:
+            return counts
+        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, ext.frame,
+                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        mean_b, var_b, _ = self.trace_pixel_lists(uniform, cameras, e, pixels, offsets, frame_keys, var=True)
+        f, j, i = fji[:, 0], fji[:, 1], fji[:, 2]
+        mean, v, cnt = merge_samples(color[f, j, i, :3], var[f, j, i], count[f, j, i], mean_b[:, :3], var_b,
+                                     float(extra_spp))
+        color[f, j, i, :3] = mean
+        var[f, j, i] = v
+        count[f, j, i] = cnt
+        return counts
+
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest
         trace_tile* call that failed on the GPU and was not reported yet (the
@@ -877,6 +955,42 @@ def select_noisy(color, var, count, rel_tol: float, floor: float = 1e-3, ids=Non
         sel = sel & (ids != miss) & (ids != failed)
     ji = torch.nonzero(sel)
     return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
+
+
+def _select_noisy_frames(color, var, count, rel_tol, floor, ids, x0, y0):
+    """select_noisy_frames' (pixels, offsets) and the (N, 3) rows (f, j, i) of
+    the selected pixels, frame-major and row-major."""
+    import torch
+
+    if color.dim() != 4 or color.shape[-1] < 3:
+        raise ValueError("color must be (n, h, w, 4) frames")
+    lead = color.shape[:3]
+    var = var.reshape(lead)
+    if torch.is_tensor(count):
+        count = count.reshape(lead)
+    sel = torch.sqrt(var / count) > rel_tol * (_lum(color) + floor)
+    if ids is not None:
+        ids = ids.reshape(lead)
+        miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)
+        sel = sel & (ids != miss) & (ids != failed)
+    fji = torch.nonzero(sel)  # (N, 3) rows of (f, j, i): frame-major, then row-major
+    pixels = torch.stack((fji[:, 2] + x0, fji[:, 1] + y0), dim=1).to(torch.int32).contiguous()
+    per_frame = torch.bincount(fji[:, 0], minlength=lead[0])
+    offsets = np.zeros(lead[0] + 1, dtype=np.uint64)
+    offsets[1:] = torch.cumsum(per_frame, 0).cpu().numpy()
+    return pixels, offsets, fji
+
+
+def select_noisy_frames(color, var, count, rel_tol: float, floor: float = 1e-3, ids=None, x0: int = 0, y0: int = 0):
+    """select_noisy() for a batch of frames at once, the lists
+    Renderer.refine_frames traces: `color` (n, h, w, 4), `var` (n, h, w),
+    `count` a scalar or (n, h, w), `ids` None or the frames' id buffers.
+    Returns (pixels, offsets): the frames' select_noisy lists back to back,
+    an (N, 2) int32 tensor on color's device, and the n + 1 offsets of the
+    lists in it as a uint64 numpy array (one read-back for the whole batch),
+    as Renderer.trace_pixel_lists takes them.  Works on CPU tensors too."""
+    pixels, offsets, _ = _select_noisy_frames(color, var, count, rel_tol, floor, ids, x0, y0)
+    return pixels, offsets
 
 
 def merge_samples(mean_a, var_a, n_a, mean_b, var_b, n_b):

@@ -43,20 +43,23 @@ being the topped-up frame before it, so the extra samples stay in the history;
 the share of pixels topped up is printed per frame.
 
 --refine TOL[:SPP[:ROUNDS]] also writes frame_NNNN_ref.png beside each frame: the
-frame after up to ROUNDS (default 2) rounds of Renderer.refine, each giving the
-pixels whose mean's standard error is above TOL times their luminance SPP more
-samples (default 3 x --spp) through mm_trace_pixels_var, drawn with RNG frame
-2^20 + 64 f + round.  The frames are then traced one by one through
-Renderer.trace_tile_var (mm_trace_tile_var: the frame and its per-pixel sample
-variance); the share of pixels each round took is printed per frame.  With
+frame after up to ROUNDS (default 2) rounds of Renderer.refine_frames, each
+giving the pixels whose mean's standard error is above TOL times their luminance
+SPP more samples (default 3 x --spp), drawn with RNG frame 2^20 + 64 f + round:
+one selection, one mm_trace_pixel_lists launch and one merge per round for the
+whole batch (the files are those of Renderer.refine frame by frame).  The batch
+is then traced with its per-pixel sample variance through Renderer.trace_tile_var
+(mm_trace_tile_var), in one launch where --accumulate-var's rule below allows
+it, else frame by frame; the share of pixels each round took is printed per frame.  With
 --denoise the denoiser runs on the refined frames.  Not with --accumulate: a
 history of frames with unequal sample counts is not what mm_accumulate_frames
 averages.
 
 --denoise-var also writes frame_NNNN_dnv.png beside each frame: the frame through
 Renderer.denoise_var (mm_denoise_frames_var, its defaults), whose luminance stop
-follows each pixel's own noise.  The frames are then traced one by one through
-Renderer.trace_tile_var, as with --refine, and with --refine the filter runs on
+follows each pixel's own noise.  The frames are then traced through
+Renderer.trace_tile_var (one by one, unless --refine or --accumulate-var trace
+the batch in one launch), and with --refine the filter runs on
 the refined frames with the variance and the sample counts the rounds left.  Not
 with --accumulate: mm_accumulate_frames carries no variance through the history
 (--accumulate-var does).
@@ -67,7 +70,7 @@ frame_NNNN_accv.png beside each frame: the frame through Renderer.accumulate_var
 the variance of every accumulated pixel carried beside it.  The batch is traced
 with its per-pixel sample variance, in one Renderer.trace_tile_var launch where
 a multi-frame variance launch runs (2^24 .. 2^29 paths: tail deferral on, the
-staged paths of a launch), else (and with --refine) frame by frame.
+staged paths of a launch), else frame by frame.
 It composes with --denoise (the denoiser runs on the accumulated frames), with
 --denoise-var (the filter takes the accumulated variance, count 1, at sigma_l 2:
 the sweep of profiles/temporal_var/quality.txt), with
@@ -205,7 +208,7 @@ def main(argv=None) -> int:
             # stages, and the tail deferral such a launch needs (from MM_OPT_DEFER_MIN's 2^24 paths on, where the
             # plan has it; the call refuses the launch otherwise, before anything is enqueued)
             paths = len(batch) * a.width * a.height * a.spp
-            one_var_launch = a.accumulate_var and refine is None and len(batch) > 1 and 2**24 <= paths <= 2**29
+            one_var_launch = (a.accumulate_var or refine is not None) and len(batch) > 1 and 2**24 <= paths <= 2**29
             if one_var_launch:
                 try:
                     img, var, _ = r.trace_tile_var(u, e, 0, 0, a.width, a.height, cameras=batch)
@@ -219,11 +222,9 @@ def main(argv=None) -> int:
                 img = torch.empty((len(batch), a.height, a.width, 4), dtype=torch.float32, device="cuda:0")
                 var = torch.empty((len(batch), a.height, a.width), dtype=torch.float32, device="cuda:0")
                 count = torch.full_like(var, float(a.spp))  # the samples each pixel holds
-                us = []
                 for k in range(len(batch)):
                     uk = mm_uniform.from_buffer_copy(u)
                     uk.cam = mm_camera.from_buffer_copy(np.ascontiguousarray(batch[k], dtype=np.float32).tobytes())
-                    us.append(uk)
                     r.trace_tile_var(uk, make_ext(a.spp, a.bounces, a.mirrors, frame=f0 + k), 0, 0, a.width, a.height,
                                      out=img[k], var=var[k])
             else:
@@ -235,16 +236,21 @@ def main(argv=None) -> int:
             print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if with_var and not one_var_launch else 'one launch'}, "
                   f"{out_dir}/frame_{f0:04d}.png ...", flush=True)
             if refine:
+                # the whole batch per round: one selection, one list launch (mm_trace_pixel_lists), one merge.  A
+                # frame that selects nothing in a round selects nothing in the later ones either: its rounds end
+                shares = [[] for _ in batch]
+                for rnd in range(refine[2]):
+                    n_sel = r.refine_frames(u, batch, e, img, var, count, refine[0], refine[1],
+                                            [2**20 + 64 * (f0 + k) + rnd for k in range(len(batch))])
+                    for k in range(len(batch)):
+                        if not (shares[k] and shares[k][-1] == 0):
+                            shares[k].append(n_sel[k])
+                    if not any(n_sel):
+                        break
                 for k in range(len(batch)):
-                    shares = []
-                    for rnd in range(refine[2]):
-                        n_sel = r.refine(us[k], e, img[k], var[k], count[k], refine[0], refine[1],
-                                         2**20 + 64 * (f0 + k) + rnd)
-                        shares.append(f"{100.0 * n_sel / (a.width * a.height):.2f} %")
-                        if n_sel == 0:
-                            break
+                    shares[k] = [f"{100.0 * n / (a.width * a.height):.2f} %" for n in shares[k]]
                     print(f"# frame {f0 + k}: refined with {refine[1]} spp per round, pixels per round: "
-                          f"{', '.join(shares)}", flush=True)
+                          f"{', '.join(shares[k])}", flush=True)
                 done = r.quantize(img).cpu().numpy()
                 r.sync()
                 for k in range(len(batch)):
