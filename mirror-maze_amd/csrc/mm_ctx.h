@@ -1,7 +1,9 @@
 // mm_ctx.h — the context behind the C ABI's opaque mm_ctx (include/mm_api.h),
-// shared by the runtime (mm_runtime.hip), the frame filters' calls
-// (mm_filters.hip) and the multi-GPU frame path (mm_comm.hip), with the three
-// files' error plumbing (fail, HIPC, ensure).  Private to the library.
+// shared by the runtime (mm_runtime.hip), the trace and query calls
+// (mm_trace_calls.hip), the frame filters' calls (mm_filters.hip) and the
+// multi-GPU frame path (mm_comm.hip), with the four files' error plumbing
+// (fail, HIPC, ensure) and the runtime's helpers the trace calls share.
+// Private to the library.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,8 +15,11 @@
 #include "mm_api.h"
 #include "mm_calls.h"
 #include "mm_launch.h"
+#include "mm_stage_ring.h"
 
 using mm::DevGrid;
+
+constexpr uint32_t kStatusSlots = 1024;
 
 struct mm_ctx {
     int device = 0;
@@ -61,17 +66,12 @@ struct mm_ctx {
     // mirror-tail rings' records (MM_OPT_DEFER)
     void* d_tail = nullptr;
     uint32_t tail_cap = 0;
-    // camera records of mm_trace_tile_cameras launches (mm::kCamStride floats each): a pinned host staging
-    // ring and its device mirror, `cams_cap` records each, filled from `cams_next` on (mm_runtime.hip
-    // stage_cameras)
-    float* h_cams = nullptr;
-    float* d_cams = nullptr;
-    size_t cams_cap = 0, cams_next = 0;
-    // list tables of mm_trace_pixel_lists launches (mm_launch.h ListTable): the same arrangement, in 32-bit
-    // words (mm_runtime.hip stage_lists)
-    uint32_t* h_lists = nullptr;
-    uint32_t* d_lists = nullptr;
-    size_t lists_cap = 0, lists_next = 0;
+    // the staging rings (mm_stage_ring.h; mm_trace_calls.hip stage): the camera records of mm_trace_tile_cameras
+    // and mm_trace_aov launches (mm::kCamStride floats each; at least 8 records, wrapping from 4096 on), and the
+    // list tables of mm_trace_pixel_lists launches (mm_launch.h ListTable; at least 1024 words, wrapping from
+    // 2^22 on).  Two rings: a table never waits for camera records' launches, nor the other way round.
+    mm::StageRing cams{8 * mm::kCamStride, 4096 * mm::kCamStride};
+    mm::StageRing lists{1024, 1u << 22};
     // mm_denoise_frames' scratch (mm_filters.hip dn_begin): the two intermediate images a frame's passes alternate between (one frame
     // each, `dn_img_cap` pixels in all) and the call's packed key records (`dn_keys_cap`).  A call's kernels are
     // ordered after the last call's on the same stream; `dn_done` (recorded after every call) orders them when
@@ -159,4 +159,14 @@ int ensure(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
     cap = n;
     return MM_OK;
 }
+
+// The runtime's helpers the trace and query calls use too (mm_runtime.hip).
+DevScene dev_scene(const mm_ctx* c);
+// The events around a call's launches (mm_last_timing).
+int begin_timing(mm_ctx* c);
+int end_timing(mm_ctx* c, uint32_t launches);
+// Reads the statistics (st, if not null) and the sticky error flag back, after a sync of the stream.
+int read_aux(mm_ctx* c, mm_stats* st);
+// An earlier call that failed on the GPU is reported first, by name (mm_calls.h).
+int report_failure(mm_ctx* c, const char* suffix);
 }  // namespace mm

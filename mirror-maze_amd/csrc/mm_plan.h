@@ -1,7 +1,7 @@
 // mm_plan.h — the launch policy of the trace calls as pure functions of scene
 // facts, options and the tile: which query method, which LDS placement, tail
 // deferral and its ring kind, fused resolve, rows per launch.  Plain C++ (no
-// HIP): mm_runtime.hip gathers the inputs and carries the plan out.
+// HIP): mm_trace_calls.hip gathers the inputs and carries the plan out.
 #pragma once
 
 #include <cstddef>

@@ -1,5 +1,6 @@
-// mm_runtime.hip — the C ABI of include/mm_api.h over the HIP runtime (the
-// frame filters' six calls: mm_filters.hip; the multi-GPU path: mm_comm.hip).
+// mm_runtime.hip — the C ABI of include/mm_api.h over the HIP runtime: the context, its options, the scene,
+// the parity path (mm_trace_chunks, present, read-backs), sync, status and timing.  (The trace and query calls:
+// mm_trace_calls.hip; the frame filters' six calls: mm_filters.hip; the multi-GPU path: mm_comm.hip.)
 //
 // Replaces the reference's Metal plumbing: device/queue creation
 // (src/main.rs:616-626), buffer creation and updates (src/utils.rs:86-102,
@@ -20,12 +21,9 @@
 #include <vector>
 
 #include "grid_build.h"
-#include "mm_aov.h"
 #include "mm_api.h"
 #include "mm_ctx.h"
-#include "mm_filter_args.h"
 #include "mm_launch.h"
-#include "mm_plan.h"
 
 using namespace mm;
 
@@ -34,9 +32,8 @@ size_t build_compact_rects(const mm_rect* rects, uint32_t n_rects, const uint32_
                            size_t* n_slow);
 }
 
-constexpr uint32_t kStatusSlots = 1024;
-
-namespace {
+// The helpers the trace and query calls (mm_trace_calls.hip) share with this file: declared in mm_ctx.h.
+namespace mm {
 
 DevScene dev_scene(const mm_ctx* c) {
     DevScene s;
@@ -54,25 +51,35 @@ DevScene dev_scene(const mm_ctx* c) {
     return s;
 }
 
-// The policy's inputs (mm_plan.h) from the context.
-SceneFacts scene_facts(const mm_ctx* c) {
-    SceneFacts f;
-    f.grid_ok = c->grid_ok; f.grid_slow = c->grid_slow; f.grid_wide = c->grid_wide; f.grid_flat = c->grid_flat;
-    f.lean_ok = c->lean_ok;
-    f.n_nodes = c->n_nodes; f.n_rects = c->n_rects;
-    f.bytes = c->grid.bytes; f.off_box = c->grid.off_box; f.off_data = c->grid.off_data;
-    f.grid_why = c->grid_why.c_str();
-    return f;
+int begin_timing(mm_ctx* c) {
+    HIPC(c, hipEventRecord(c->ev0, c->stream));
+    return MM_OK;
 }
-PlanOptions plan_options(const mm_ctx* c) {
-    PlanOptions o;
-    o.pipe = c->pipe; o.opt_ww = c->opt_ww; o.opt_lds = c->opt_lds; o.opt_lds_rects = c->opt_lds_rects;
-    o.opt_fuse = c->opt_fuse; o.opt_persist = c->opt_persist; o.opt_defer = c->opt_defer;
-    o.opt_defer_min = c->opt_defer_min;
-    o.opt_predraw = c->opt_predraw;
-    o.opt_predraw_pool = c->opt_predraw_pool;
-    return o;
+int end_timing(mm_ctx* c, uint32_t launches) {
+    HIPC(c, hipEventRecord(c->ev1, c->stream));
+    c->last_launches = launches;
+    c->last_ms = -1.0f;  // resolved lazily in mm_last_timing
+    return MM_OK;
 }
+
+int read_aux(mm_ctx* c, mm_stats* st) {
+    unsigned long long h[5];
+    HIPC(c, hipMemcpyAsync(h, c->d_aux, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (st) { st->rays = h[0]; st->node_visits = h[1]; st->rect_tests = h[2]; st->paths = h[3]; }
+    if ((uint32_t)h[4] != 0) {
+        HIPC(c, hipMemsetAsync(c->d_aux + 4, 0, sizeof(unsigned long long), c->stream));
+        if (h[4] & 2u) return fail(c, MM_ERR_HIP, "tail ring wait timed out (kernel protocol error)");
+        return fail(c, MM_ERR_STACK, "traversal stack overflow (depth > 50)");
+    }
+    return MM_OK;
+}
+
+int report_failure(mm_ctx* c, const char* suffix) { return c->calls.report_failure(suffix, c->err); }
+
+}  // namespace mm
+
+namespace {
 
 void free_scene(mm_ctx* c) {
     (void)hipFree(c->d_rects); (void)hipFree(c->d_nodes); (void)hipFree(c->d_nodes_ref); (void)hipFree(c->d_geo);
@@ -122,176 +129,6 @@ bool coord_ok(float x) {
 bool extent_ok(float x) {
     const float a = std::fabs(x);
     return a == 0.0f || (a >= 0x1p-10f && a <= 0x1p60f);
-}
-
-// The tail rings' records (mm_launch.h TailQueue): kTailRing per resident
-// block, at most 2 blocks per CU.
-int tail_queue(mm_ctx* c, TailQueue& q) {
-    int cus = 0;
-    HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    const uint32_t cap = 2u * (uint32_t)cus * kTailRing;
-    if (c->tail_cap < cap || !c->d_tail) {
-        (void)hipFree(c->d_tail);
-        c->d_tail = nullptr;
-        c->tail_cap = 0;
-        HIPC(c, hipMalloc(&c->d_tail, (size_t)cap * 64));
-        c->tail_cap = cap;
-    }
-    q.rec = reinterpret_cast<uint4*>(c->d_tail);
-    q.cap = c->tail_cap;
-    return MM_OK;
-}
-
-// The device records of a camera-sequence launch (mm_launch.h TileJob::cams): the caller's cameras go into a
-// pinned staging ring (consumed when this returns) and from there to the ring's device mirror by a copy on
-// the context's stream, ahead of the launch that reads them.  Every call takes fresh records, so a later
-// call's cameras never land on those of a launch still running, and nothing here waits for the GPU -- except
-// when the ring is full: then everything the device has queued is waited for once, and the ring grows (up to
-// kCamsWrap records, from where on it wraps instead).
-constexpr size_t kCamsMin = 8, kCamsWrap = 4096;
-int stage_cameras(mm_ctx* c, const mm_camera* cams, uint32_t n, const float*& dev) {
-    if (c->cams_next + n > c->cams_cap) {
-        HIPC(c, hipDeviceSynchronize());  // staged records may still be on their way, on any stream used so far
-        if (n > c->cams_cap || c->cams_cap < kCamsWrap) {
-            const size_t cap = std::max<size_t>({kCamsMin, 2 * c->cams_cap, n});
-            if (c->h_cams) (void)hipHostFree(c->h_cams);
-            (void)hipFree(c->d_cams);
-            c->h_cams = nullptr; c->d_cams = nullptr; c->cams_cap = 0;
-            HIPC(c, hipHostMalloc((void**)&c->h_cams, cap * kCamStride * sizeof(float), hipHostMallocDefault));
-            HIPC(c, hipMalloc((void**)&c->d_cams, cap * kCamStride * sizeof(float)));
-            c->cams_cap = cap;
-        }
-        c->cams_next = 0;
-    }
-    float* h = c->h_cams + c->cams_next * kCamStride;
-    std::memset(h, 0, (size_t)n * kCamStride * sizeof(float));
-    for (uint32_t f = 0; f < n; ++f) std::memcpy(h + (size_t)f * kCamStride, &cams[f], sizeof(mm_camera));
-    float* d = c->d_cams + c->cams_next * kCamStride;
-    HIPC(c, hipMemcpyAsync(d, h, (size_t)n * kCamStride * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    c->cams_next += n;
-    dev = d;
-    return MM_OK;
-}
-
-// The list table of an mm_trace_pixel_lists launch (mm_launch.h ListTable), staged as stage_cameras stages
-// camera records: `words` words (a multiple of 16, so every table starts on a 64-byte line) of a pinned ring
-// that `fill` writes, mirrored to the device by a copy on the context's stream ahead of the launch.  Every
-// call takes fresh words; nothing waits for the GPU unless the ring is full (then once, and the ring grows up
-// to kListsWrap words, from where on it wraps).
-constexpr size_t kListsMin = 1024, kListsWrap = 1u << 22;
-template <typename F>
-int stage_lists(mm_ctx* c, size_t words, F&& fill, const uint32_t*& dev) {
-    if (c->lists_next + words > c->lists_cap) {
-        HIPC(c, hipDeviceSynchronize());  // staged tables may still be on their way, on any stream used so far
-        if (words > c->lists_cap || c->lists_cap < kListsWrap) {
-            const size_t cap = std::max<size_t>({kListsMin, 2 * c->lists_cap, words});
-            if (c->h_lists) (void)hipHostFree(c->h_lists);
-            (void)hipFree(c->d_lists);
-            c->h_lists = nullptr; c->d_lists = nullptr; c->lists_cap = 0;
-            HIPC(c, hipHostMalloc((void**)&c->h_lists, cap * sizeof(uint32_t), hipHostMallocDefault));
-            HIPC(c, hipMalloc((void**)&c->d_lists, cap * sizeof(uint32_t)));
-            c->lists_cap = cap;
-        }
-        c->lists_next = 0;
-    }
-    uint32_t* h = c->h_lists + c->lists_next;
-    std::memset(h, 0, words * sizeof(uint32_t));
-    fill(h);
-    uint32_t* d = c->d_lists + c->lists_next;
-    HIPC(c, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    c->lists_next += words;
-    dev = d;
-    return MM_OK;
-}
-
-int begin_timing(mm_ctx* c) {
-    HIPC(c, hipEventRecord(c->ev0, c->stream));
-    return MM_OK;
-}
-int end_timing(mm_ctx* c, uint32_t launches) {
-    HIPC(c, hipEventRecord(c->ev1, c->stream));
-    c->last_launches = launches;
-    c->last_ms = -1.0f;  // resolved lazily in mm_last_timing
-    return MM_OK;
-}
-
-// Bracket one trace-kernel launch with events when profiling is on.
-int prof_mark(mm_ctx* c) {
-    if (!c->prof) return MM_OK;
-    if (c->prof_used == c->prof_ev.size()) {
-        hipEvent_t e;
-        HIPC(c, hipEventCreate(&e));
-        c->prof_ev.push_back(e);
-    }
-    HIPC(c, hipEventRecord(c->prof_ev[c->prof_used++], c->stream));
-    return MM_OK;
-}
-
-int read_aux(mm_ctx* c, mm_stats* st) {
-    unsigned long long h[5];
-    HIPC(c, hipMemcpyAsync(h, c->d_aux, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (st) { st->rays = h[0]; st->node_visits = h[1]; st->rect_tests = h[2]; st->paths = h[3]; }
-    if ((uint32_t)h[4] != 0) {
-        HIPC(c, hipMemsetAsync(c->d_aux + 4, 0, sizeof(unsigned long long), c->stream));
-        if (h[4] & 2u) return fail(c, MM_ERR_HIP, "tail ring wait timed out (kernel protocol error)");
-        return fail(c, MM_ERR_STACK, "traversal stack overflow (depth > 50)");
-    }
-    return MM_OK;
-}
-
-// ---- per-call status (mm_calls.h) -------------------------------------------
-// An earlier call that failed on the GPU is reported first, by name.
-int report_failure(mm_ctx* c, const char* suffix) { return c->calls.report_failure(suffix, c->err); }
-
-// One launch of the open call (CallTracker::begin_call): takes its status slot, runs
-// launch(status word, launch id) -- which enqueues the kernel and returns MM_OK or what fail() gave it --
-// and, unless the kernel publishes its status itself (self_publish: the wave-persistent kernel's last wave
-// does), enqueues the publish of the error flag into the status word.  The slot is taken first (its device
-// address is a kernel argument); if the launch then fails to enqueue, the slot is released as
-// finished-clean, and the call is still tracked for the launches it did enqueue.
-template <typename L>
-int enqueue_launch(mm_ctx* c, bool self_publish, L&& launch) {
-    uint32_t slot = 0;
-    if (int rc = c->calls.next_status(slot, c->err)) return rc;
-    int rc = prof_mark(c);
-    if (!rc) rc = launch(c->d_status + slot, (uint32_t)c->calls.last_launch());
-    if (rc) {
-        c->calls.release_unqueued();
-        return rc;
-    }
-    if (!self_publish) {
-        uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-        const hipError_t pe = launch_publish_status(err_dev, c->d_status + slot, c->stream);
-        if (pe != hipSuccess) {
-            // fold the kernel's error flag into THIS launch's slot (after a sync), so it is
-            // never published by -- and blamed on -- a later call's launch
-            uint32_t bits = 0;
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipMemcpy(&bits, err_dev, sizeof(bits), hipMemcpyDeviceToHost);
-            (void)hipMemset(err_dev, 0, sizeof(bits));
-            c->calls.fold_unpublished(bits);
-            return fail(c, MM_ERR_HIP, std::string("launch_publish_status: ") + hipGetErrorString(pe));
-        }
-    }
-    return prof_mark(c);
-}
-
-// The view and tile checks shared by the trace calls; `name` prefixes the messages.  e: the sampling
-// parameters of a call that has them (mm_trace_tile*), else null and the call's own mirror limit.
-int check_tile(mm_ctx* c, const char* name, const mm_uniform* u, const mm_ext* e, uint32_t mirror_limit, uint32_t x0,
-               uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride) {
-    auto bad = [&](const char* what) { return fail(c, MM_ERR_INVALID, std::string(name) + ": " + what); };
-    if (!(u->view_w >= 1.0f && u->view_w <= 65536.0f && u->view_h >= 1.0f && u->view_h <= 65536.0f))
-        return bad("bad view size");
-    const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
-    if (w == 0 || h == 0 || y_stride == 0 || (e && (e->spp == 0 || e->spp > 4096)))
-        return bad(e ? "empty tile or bad spp" : "empty tile");
-    // the tail records pack bounces | mirror hits << 16 (trace_kernels.hip tail_store)
-    if ((e && e->bounce_limit > 32767) || mirror_limit > 32767)
-        return bad(e ? "bounce or mirror limit above 32767" : "mirror limit above 32767");
-    if ((uint64_t)x0 + w > W || (uint64_t)y0 + (uint64_t)(h - 1) * y_stride >= H) return bad("tile outside the frame");
-    return MM_OK;
 }
 
 }  // namespace
@@ -353,10 +190,10 @@ void mm_destroy(mm_ctx* c) {
     (void)hipFree(c->d_fb8_alt); (void)hipFree(c->d_packets);
     (void)hipFree(c->d_samples); (void)hipFree(c->d_aux); (void)hipFree(c->d_tail); (void)hipFree(c->d_work);
     (void)hipFree(c->d_gather);
-    (void)hipFree(c->d_cams);
-    if (c->h_cams) (void)hipHostFree(c->h_cams);
-    (void)hipFree(c->d_lists);
-    if (c->h_lists) (void)hipHostFree(c->h_lists);
+    for (StageRing* r : {&c->cams, &c->lists}) {
+        (void)hipFree(r->dev);
+        if (r->host) (void)hipHostFree(r->host);
+    }
     (void)hipFree(c->d_dn_img); (void)hipFree(c->d_dn_keys); (void)hipFree(c->d_dn_var);
     if (c->dn_done) (void)hipEventDestroy(c->dn_done);
     if (c->gather_done) (void)hipEventDestroy(c->gather_done);
@@ -709,595 +546,6 @@ int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
     if (rgba8) HIPC(c, hipMemcpyAsync(rgba8, c->d_fb8, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     return MM_OK;
-}
-
-namespace {
-
-// The additional conditions of the variance calls (name: mm_trace_tile_var / mm_trace_pixels_var): at least
-// two samples, no accumulation, and a variance buffer of n floats apart from the output's out_bytes.
-int check_var(mm_ctx* c, const char* name, const mm_ext* e, const void* out_dev, uint64_t out_bytes,
-              const float* var_dev, uint64_t n) {
-    auto bad = [&](const char* what) { return fail(c, MM_ERR_INVALID, std::string(name) + ": " + what); };
-    if (e->spp < 2) return bad("a sample variance needs spp >= 2");
-    if (e->flags & MM_EXT_ACCUMULATE) return bad("MM_EXT_ACCUMULATE is not supported");
-    if (!var_dev) return bad("null var_dev");
-    if (reinterpret_cast<uintptr_t>(var_dev) % 4) return bad("var_dev not 4-byte aligned");
-    if (ranges_overlap(out_dev, out_bytes, var_dev, n * 4)) return bad("var_dev overlaps out_dev");
-    return MM_OK;
-}
-
-// cams: null, or the n_frames cameras of a camera-sequence launch (mm_trace_tile_cameras; u->cam is then unused)
-// var_call: mm_trace_tile_var -- the samples are staged whatever MM_OPT_FUSE_RESOLVE says, and the resolve
-// writes the per-pixel variance to var_dev beside the pixel
-int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
-                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, void* out_dev,
-                    mm_stats* stats, bool var_call = false, float* var_dev = nullptr) {
-    if (!c) return MM_ERR_INVALID;
-    // the multi-frame entry point this call came through (its conditions apply to a one-camera sequence too)
-    const bool multi = n_frames > 1 || cams;
-    const char* fn = cams ? "mm_trace_tile_cameras" : "mm_trace_tile_frames";
-    // an earlier call that failed on the GPU is reported first, by name; this call is then not enqueued
-    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
-    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_tile: no scene uploaded");
-    if (!u || !e || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_tile: null argument");
-    if (int rc0 = check_tile(c, "mm_trace_tile", u, e, e->mirror_limit, x0, y0, w, h, y_stride)) return rc0;
-    if (n_frames == 0) return fail(c, MM_ERR_INVALID, std::string(fn) + ": no frames");
-    // MM_EXT_RGBA8: 4-byte RGBA8 pixels (the fused texture-write conversion) instead of float4
-    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
-    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
-        return fail(c, MM_ERR_INVALID, "mm_trace_tile: MM_EXT_RGBA8 frames cannot accumulate");
-    const size_t out_bpp = rgba8 ? 4 : 16;
-    // the stores are out_bpp wide (a float4 per pixel, or one RGBA8 word): the output must be aligned to that
-    if (reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
-        return fail(c, MM_ERR_INVALID, std::string("mm_trace_tile: output not ") + std::to_string(out_bpp) +
-                                           "-byte aligned");
-    if (var_call) {
-        // (elements in all, capped where the plan refuses the launch anyway: the byte counts fit 64 bits)
-        const uint64_t n_all = std::min<uint64_t>((uint64_t)w * h, (1ull << 40) / n_frames) * n_frames;
-        if (int rc0 = check_var(c, "mm_trace_tile_var", e, out_dev, n_all * out_bpp, var_dev, n_all)) return rc0;
-    }
-    HIPC(c, hipSetDevice(c->device));
-    const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
-    const bool persist = c->pipe != MM_PIPE_REFERENCE && (c->pipe == MM_PIPE_WAVEFRONT || c->opt_persist == 2);
-    if (!persist && c->pipe != MM_PIPE_REFERENCE) return fail(c, MM_ERR_UNSUPPORTED, kRemoved);
-    // the plan (mm_plan.h): query method and LDS placement, then deferral / ring kind / fused resolve / rows
-    // per launch, given the static LDS of the placement's deferral kernels
-    const SceneFacts facts = scene_facts(c);
-    PlanOptions opts = plan_options(c);
-    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
-    int form = 0, mode = 0;
-    if (persist) {
-        Choice m = choose_method(facts, opts);
-        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
-        if (m.code != MM_OK) return fail(c, m.code, m.error);
-        form = m.form;
-        mode = m.mode;
-    }
-    size_t static_lds[2] = {kNotBuilt, kNotBuilt};
-    if (persist && wavepersist_defer_built(mode, form) && (c->opt_defer != 0 || c->pipe == MM_PIPE_WAVEFRONT))
-        for (int kind : {1, 2}) {
-            hipFuncAttributes a{};
-            // (a static-grid placement is fitted to the array's capacity: the kernel's own figure is not read)
-            if (lds_static_grid(mode)) static_lds[kind - 1] = 0;
-            else if (wavepersist_attributes(mode, form, kind, &a) == hipSuccess) static_lds[kind - 1] = a.sharedSizeBytes;
-        }
-    const LaunchPlan plan = plan_tile(facts, opts, form, mode, static_lds, *e, w, h, n_frames, multi ? fn : nullptr);
-    if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
-    const bool defer = plan.defer, fuse = plan.fuse;
-    const uint32_t rows_per_batch = plan.rows_per_batch;
-    const uint64_t row_paths = (uint64_t)w * e->spp;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap,
-                                   (size_t)(row_paths * rows_per_batch) * (defer ? n_frames : 1));
-    if (rc) return rc;
-    TailQueue tq;
-    if (defer && plan.ring == 1 && (rc = tail_queue(c, tq))) return rc;  // (records in LDS: no global ring)
-    const float* cams_dev = nullptr;
-    if (cams && (rc = stage_cameras(c, cams, n_frames, cams_dev))) return rc;
-    // aux: [0..3] stats (zeroed only when counted), [4] error flag (moved into the launch's status word by
-    // the launch itself).  d_work: the wave-persistent kernel's queue head(s) and waves-done word
-    // (self-cleaning).  No fill kernel on the default path: see k_trace_wavepersist.
-    if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
-    if ((rc = begin_timing(c))) return rc;
-    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-    const DevScene sc = dev_scene(c);
-    c->calls.begin_call();
-    uint32_t launches = 0;
-    for (uint32_t j0 = 0; j0 < h; j0 += rows_per_batch) {
-        TileJob job;
-        job.u = *u;
-        job.e = *e;
-        job.x0 = x0;
-        job.y0 = y0 + j0 * y_stride;
-        job.w = w;
-        job.h = std::min(rows_per_batch, h - j0);
-        job.y_stride = y_stride;
-        job.view_w = (uint32_t)u->view_w;
-        job.fuse = fuse ? 1u : 0u;
-        job.wave_ts = c->d_wave_ts;
-        job.wave_ts_cap = c->wave_ts_cap;
-        job.out = reinterpret_cast<char*>(out_dev) + (size_t)j0 * w * out_bpp;
-        job.n_frames = n_frames;
-        job.cams = cams_dev;
-        job.reserve_cus = c->opt_reserve_cus;
-        job.predraw = plan.predraw;
-        job.predraw_pool = plan.predraw_pool;
-        job.fault = (c->opt_fault == 1 || c->opt_fault == 4) ? (uint32_t)c->opt_fault : 0u;
-        if (c->opt_fault == 2) job.ring_spin = 0;
-        if (defer) {
-            job.defer_from = 1;
-            job.defer_lanes = c->opt_defer > 0 ? (uint32_t)c->opt_defer : 32u;
-            job.tail = tq;
-            job.ring_lds = plan.ring == 2 ? 1u : 0u;
-        }
-        job.ring_diag = c->d_status + kStatusSlots;
-        rc = enqueue_launch(c, persist, [&](uint32_t* status, uint32_t launch_id) -> int {
-            job.status = status;
-            job.launch_id = launch_id;
-            if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
-            if (persist) {
-                c->last_form = form >= kFormGrid ? kFormGrid : form;
-                c->last_mode = mode;
-                c->last_kern_mode = mode;
-                c->last_kern_form = form;
-                c->last_kern_ring = plan.ring;
-                HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev,
-                                                 c->d_work, want_stats, mode, form,
-                                                 c->stream));
-            } else {
-                MegaOpts mo;
-                mo.reference = c->pipe == MM_PIPE_REFERENCE;
-                mo.block = c->opt_block ? c->opt_block : 256u;
-                HIPC(c, launch_trace_mega(dev_scene(c), job, c->d_samples, c->d_aux, err_dev, want_stats, mo,
-                                          c->stream));
-            }
-            return MM_OK;
-        });
-        if (rc) break;
-        launches += fuse ? 1 : 2;
-        if (fuse) continue;
-        // the frames' staged samples and output slices are contiguous (a multi-frame launch is one
-        // row batch), so one resolve over h x n_frames rows covers them all
-        TileJob rj = job;
-        if (defer) rj.h = job.h * n_frames;
-        // (a later row batch's variances start at its own rows)
-        const hipError_t re =
-            var_call ? launch_resolve_var(rj, c->d_samples, job.out, var_dev + (size_t)j0 * w, c->stream)
-                     : launch_resolve(rj, c->d_samples, job.out, c->stream);
-        if (re != hipSuccess) {
-            rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
-            break;
-        }
-    }
-    c->last_defer = defer;
-    char what[160] = "";
-    if (c->calls.call_has_launches())  // the launches this call enqueued (all of them unless rc)
-        snprintf(what, sizeof(what), "%s, frames %u..%u, tile (%u, %u) %ux%u / %u, %u spp",
-                 var_call ? "mm_trace_tile_var" : multi ? fn : "mm_trace_tile", e->frame, e->frame + n_frames - 1, x0,
-                 y0, w, h, y_stride, e->spp);
-    c->calls.end_call(what);
-    if (rc) return rc;
-    if ((rc = end_timing(c, launches))) return rc;
-    if (want_stats) {
-        if ((rc = read_aux(c, stats))) return rc;
-        return report_failure(c, "");  // (synced: this call's own error, if any)
-    }
-    return MM_OK;
-}
-
-}  // namespace
-
-int mm_trace_tile(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t x0, uint32_t y0, uint32_t w,
-                  uint32_t h, uint32_t y_stride, float* out_dev, mm_stats* stats) {
-    return trace_tile_impl(c, u, nullptr, e, 1, x0, y0, w, h, y_stride, out_dev, stats);
-}
-
-int mm_trace_tile_frames(mm_ctx* c, const mm_uniform* u, const mm_ext* e, uint32_t n_frames, uint32_t x0,
-                         uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev, mm_stats* stats) {
-    return trace_tile_impl(c, u, nullptr, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
-}
-
-int mm_trace_tile_cameras(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
-                          uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, float* out_dev,
-                          mm_stats* stats) {
-    if (!c) return MM_ERR_INVALID;
-    if (!cams) return fail(c, MM_ERR_INVALID, "mm_trace_tile_cameras: no cameras");
-    return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats);
-}
-
-int mm_trace_tile_var(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e, uint32_t n_frames,
-                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, void* out_dev, float* var_dev,
-                      mm_stats* stats) {
-    return trace_tile_impl(c, u, cams, e, n_frames, x0, y0, w, h, y_stride, out_dev, stats, true, var_dev);
-}
-
-namespace {
-
-// var_call: mm_trace_pixels_var, as in trace_tile_impl
-int trace_pixels_impl(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
-                      void* out_dev, mm_stats* stats, bool var_call, float* var_dev) {
-    if (!c) return MM_ERR_INVALID;
-    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
-    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_pixels: no scene uploaded");
-    if (n_pixels == 0) return MM_OK;
-    if (!u || !e || !pixels_dev || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_pixels: null argument");
-    // (the view, spp and the limits: the tile calls' checks, on a one-pixel tile)
-    if (int rc0 = check_tile(c, "mm_trace_pixels", u, e, e->mirror_limit, 0, 0, 1, 1, 1)) return rc0;
-    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
-    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
-        return fail(c, MM_ERR_INVALID, "mm_trace_pixels: MM_EXT_RGBA8 results cannot accumulate");
-    const size_t out_bpp = rgba8 ? 4 : 16;
-    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
-        return fail(c, MM_ERR_INVALID, std::string("mm_trace_pixels: list not 8-byte or output not ") +
-                                           std::to_string(out_bpp) + "-byte aligned");
-    if (var_call) {
-        if (n_pixels > 0xFFFFFFFFull)  // (the plan's own refusal, ahead of the byte counts below)
-            return fail(c, MM_ERR_INVALID, "mm_trace_pixels: more paths than one launch holds (2^32)");
-        if (int rc0 = check_var(c, "mm_trace_pixels_var", e, out_dev, n_pixels * out_bpp, var_dev, n_pixels))
-            return rc0;
-    }
-    HIPC(c, hipSetDevice(c->device));
-    const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
-    const bool persist = c->pipe != MM_PIPE_REFERENCE && c->opt_persist == 2;
-    const SceneFacts facts = scene_facts(c);
-    PlanOptions opts = plan_options(c);
-    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
-    // the plan first: its refusals (the queue and staging bounds) need no kernel choice
-    const LaunchPlan plan = plan_pixels(opts, *e, n_pixels);
-    if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
-    int form = 0, mode = 0;
-    if (persist) {
-        Choice m = choose_method(facts, opts);
-        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
-        if (m.code != MM_OK) return fail(c, m.code, m.error);
-        form = m.form;
-        mode = m.mode;
-    }
-    const bool fuse = plan.fuse;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_pixels * e->spp));
-    if (rc) return rc;
-    if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
-    if ((rc = begin_timing(c))) return rc;
-    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-    const DevScene sc = dev_scene(c);
-    // the tile job of a one-row tile n_pixels wide, its pixels named by the list
-    TileJob job;
-    job.u = *u;
-    job.e = *e;
-    job.x0 = 0;
-    job.y0 = 0;
-    job.w = (uint32_t)n_pixels;
-    job.h = 1;
-    job.y_stride = 1;
-    job.view_w = (uint32_t)u->view_w;
-    job.fuse = fuse ? 1u : 0u;
-    job.wave_ts = c->d_wave_ts;
-    job.wave_ts_cap = c->wave_ts_cap;
-    job.out = out_dev;
-    job.reserve_cus = c->opt_reserve_cus;
-    job.predraw = plan.predraw;
-    job.predraw_pool = plan.predraw_pool;
-    job.fault = c->opt_fault == 1 ? 1u : 0u;
-    job.ring_diag = c->d_status + kStatusSlots;
-    job.list = 1;
-    job.pixels = reinterpret_cast<const uint2*>(pixels_dev);
-    c->calls.begin_call();
-    rc = enqueue_launch(c, persist, [&](uint32_t* status, uint32_t launch_id) -> int {
-        job.status = status;
-        job.launch_id = launch_id;
-        if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
-        if (persist) {
-            c->last_form = form >= kFormGrid ? kFormGrid : form;
-            c->last_mode = mode;
-            c->last_kern_mode = mode;
-            c->last_kern_form = form;
-            c->last_kern_ring = 0;
-            HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev, c->d_work, want_stats, mode,
-                                             form, c->stream));
-        } else {
-            MegaOpts mo;
-            mo.reference = true;
-            mo.block = c->opt_block ? c->opt_block : 256u;
-            HIPC(c, launch_trace_mega(sc, job, c->d_samples, c->d_aux, err_dev, want_stats, mo, c->stream));
-        }
-        return MM_OK;
-    });
-    if (!rc && !fuse) {
-        const hipError_t re = var_call ? launch_resolve_var(job, c->d_samples, job.out, var_dev, c->stream)
-                                       : launch_resolve(job, c->d_samples, job.out, c->stream);
-        if (re != hipSuccess) rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
-    }
-    c->last_defer = false;
-    char what[160] = "";
-    if (c->calls.call_has_launches())
-        snprintf(what, sizeof(what), "%s, frame %u, %llu pixels, %u spp",
-                 var_call ? "mm_trace_pixels_var" : "mm_trace_pixels", e->frame, (unsigned long long)n_pixels, e->spp);
-    c->calls.end_call(what);
-    if (rc) return rc;
-    if ((rc = end_timing(c, fuse ? 1 : 2))) return rc;
-    if (want_stats) {
-        if ((rc = read_aux(c, stats))) return rc;
-        return report_failure(c, "");
-    }
-    return MM_OK;
-}
-
-}  // namespace
-
-int mm_trace_pixels(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
-                    void* out_dev, mm_stats* stats) {
-    return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, false, nullptr);
-}
-
-int mm_trace_pixels_var(mm_ctx* c, const mm_uniform* u, const mm_ext* e, const uint32_t* pixels_dev, uint64_t n_pixels,
-                        void* out_dev, float* var_dev, mm_stats* stats) {
-    return trace_pixels_impl(c, u, e, pixels_dev, n_pixels, out_dev, stats, true, var_dev);
-}
-
-// The pixel lists of several frames in one launch: mm_trace_pixels' checks in its order, the plan
-// (mm_plan.h plan_pixel_lists), the list table staged ahead of the launch, one kList == 2 launch and, with
-// staged samples, one resolve over the concatenation as ONE list (its slots are global entry * spp + sample).
-// MM_PIPE_REFERENCE: one unchanged k_trace_mega list launch per non-empty list, each into its own slice of
-// the staged samples, and the same resolve.  var_dev: the variance call (mm_trace_pixels_var's conditions).
-int mm_trace_pixel_lists(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const mm_ext* e,
-                         const uint32_t* frame_keys, uint32_t n_lists, const uint32_t* pixels_dev,
-                         const uint64_t* offsets, void* out_dev, float* var_dev, mm_stats* stats) {
-    if (!c) return MM_ERR_INVALID;
-    const char* fn = "mm_trace_pixel_lists";
-    const bool var_call = var_dev != nullptr;
-    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
-    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_pixel_lists: no scene uploaded");
-    uint64_t n_entries = 0;
-    std::string why;
-    if (int rc0 = lists_total(offsets, n_lists, n_entries, why)) return fail(c, rc0, why);
-    if (n_entries == 0) return MM_OK;
-    if (!u || !e || !pixels_dev || !out_dev) return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: null argument");
-    if (int rc0 = check_tile(c, fn, u, e, e->mirror_limit, 0, 0, 1, 1, 1)) return rc0;
-    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
-    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE))
-        return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: MM_EXT_RGBA8 results cannot accumulate");
-    const size_t out_bpp = rgba8 ? 4 : 16;
-    if (reinterpret_cast<uintptr_t>(pixels_dev) % 8 || reinterpret_cast<uintptr_t>(out_dev) % out_bpp)
-        return fail(c, MM_ERR_INVALID, std::string("mm_trace_pixel_lists: lists not 8-byte or output not ") +
-                                           std::to_string(out_bpp) + "-byte aligned");
-    if (var_call) {
-        if (n_entries > 0xFFFFFFFFull)  // (the plan's own refusal, ahead of the byte counts below)
-            return fail(c, MM_ERR_INVALID, "mm_trace_pixel_lists: more paths than one launch holds (2^32)");
-        if (int rc0 = check_var(c, fn, e, out_dev, n_entries * out_bpp, var_dev, n_entries)) return rc0;
-    }
-    HIPC(c, hipSetDevice(c->device));
-    const bool want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
-    const bool persist = c->pipe != MM_PIPE_REFERENCE && c->opt_persist == 2;
-    const SceneFacts facts = scene_facts(c);
-    PlanOptions opts = plan_options(c);
-    if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
-    const ListsPlan lp = plan_pixel_lists(opts, *e, offsets, n_lists);
-    if (lp.plan.code != MM_OK) return fail(c, lp.plan.code, lp.plan.error);
-    int form = 0, mode = 0;
-    if (persist) {
-        Choice m = choose_method(facts, opts);
-        if (m.code == MM_OK) m = choose_placement(facts, opts, m.form);
-        if (m.code != MM_OK) return fail(c, m.code, m.error);
-        form = m.form;
-        mode = m.mode;
-    }
-    const bool fuse = lp.plan.fuse;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e->spp));
-    if (rc) return rc;
-    auto key_of = [&](uint32_t f) { return frame_keys ? frame_keys[f] : e->frame + f; };
-    auto cam_of = [&](uint32_t f) -> const mm_camera& { return cams ? cams[f] : u->cam; };
-    const uint32_t* table_dev = nullptr;
-    if (persist) {
-        rc = stage_lists(c, ListTable::words(n_lists), [&](uint32_t* t) {
-            const uintptr_t px = reinterpret_cast<uintptr_t>(pixels_dev);
-            t[ListTable::kPixLo] = (uint32_t)px;
-            t[ListTable::kPixHi] = (uint32_t)((uint64_t)px >> 32);
-            t[ListTable::kLists] = n_lists;
-            t[ListTable::kChunks] = lp.n_chunks;
-            t[ListTable::kRecords] = ListTable::records_at(n_lists);
-            for (uint32_t f = 0; f < n_lists; ++f) {
-                const ListSpan& l = lp.lists[f];
-                t[ListTable::kHeader + f] = l.first_chunk;
-                uint32_t* r = t + ListTable::records_at(n_lists) + (size_t)f * ListTable::kRecWords;
-                std::memcpy(r, &cam_of(f), sizeof(mm_camera));
-                r[ListTable::kKey] = key_of(f);
-                r[ListTable::kFirstChunk] = l.first_chunk;
-                r[ListTable::kNumChunks] = l.n_chunks;
-                r[ListTable::kFirstEntry] = l.first_entry;
-                r[ListTable::kPaths] = l.n_paths;
-                r[ListTable::kEntries] = l.n_entries;
-            }
-            t[ListTable::kHeader + n_lists] = lp.n_chunks;
-        }, table_dev);
-        if (rc) return rc;
-    }
-    if (want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
-    if ((rc = begin_timing(c))) return rc;
-    uint32_t* err_dev = reinterpret_cast<uint32_t*>(c->d_aux + 4);
-    const DevScene sc = dev_scene(c);
-    // the concatenation as one list: the resolve's job, and the base of the launches'
-    TileJob all;
-    all.u = *u;
-    all.e = *e;
-    all.x0 = 0;
-    all.y0 = 0;
-    all.w = (uint32_t)n_entries;
-    all.h = 1;
-    all.y_stride = 1;
-    all.view_w = (uint32_t)u->view_w;
-    all.fuse = fuse ? 1u : 0u;
-    all.wave_ts = c->d_wave_ts;
-    all.wave_ts_cap = c->wave_ts_cap;
-    all.out = out_dev;
-    all.reserve_cus = c->opt_reserve_cus;
-    all.predraw = lp.plan.predraw;
-    all.predraw_pool = lp.plan.predraw_pool;
-    all.fault = c->opt_fault == 1 ? 1u : 0u;
-    all.ring_diag = c->d_status + kStatusSlots;
-    all.list = 1;
-    all.pixels = reinterpret_cast<const uint2*>(pixels_dev);
-    c->calls.begin_call();
-    uint32_t launches = 0;
-    if (persist) {
-        TileJob job = all;
-        job.list = 2;
-        job.lists = table_dev;
-        rc = enqueue_launch(c, true, [&](uint32_t* status, uint32_t launch_id) -> int {
-            job.status = status;
-            job.launch_id = launch_id;
-            if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
-            c->last_form = form >= kFormGrid ? kFormGrid : form;
-            c->last_mode = mode;
-            c->last_kern_mode = mode;
-            c->last_kern_form = form;
-            c->last_kern_ring = 0;
-            HIPC(c, launch_trace_wavepersist(sc, job, c->d_samples, c->d_aux, err_dev, c->d_work, want_stats, mode,
-                                             form, c->stream));
-            return MM_OK;
-        });
-        if (!rc) ++launches;
-    } else {
-        for (uint32_t f = 0; f < n_lists && !rc; ++f) {
-            const ListSpan& l = lp.lists[f];
-            if (!l.n_entries) continue;
-            TileJob job = all;
-            job.u.cam = cam_of(f);
-            job.e.frame = key_of(f);
-            job.w = l.n_entries;
-            job.pixels = all.pixels + l.first_entry;
-            job.out = reinterpret_cast<char*>(out_dev) + (size_t)l.first_entry * out_bpp;
-            Sample* samples = c->d_samples + (size_t)l.first_entry * e->spp;
-            rc = enqueue_launch(c, false, [&](uint32_t* status, uint32_t launch_id) -> int {
-                job.status = status;
-                job.launch_id = launch_id;
-                if (c->opt_fault == 3) return fail(c, MM_ERR_HIP, "injected enqueue failure (MM_OPT_FAULT_INJECT 3)");
-                MegaOpts mo;
-                mo.reference = true;
-                mo.block = c->opt_block ? c->opt_block : 256u;
-                HIPC(c, launch_trace_mega(sc, job, samples, c->d_aux, err_dev, want_stats, mo, c->stream));
-                return MM_OK;
-            });
-            if (!rc) ++launches;
-        }
-    }
-    if (!rc && !fuse) {
-        const hipError_t re = var_call ? launch_resolve_var(all, c->d_samples, out_dev, var_dev, c->stream)
-                                       : launch_resolve(all, c->d_samples, out_dev, c->stream);
-        if (re != hipSuccess) rc = fail(c, MM_ERR_HIP, std::string("launch_resolve: ") + hipGetErrorString(re));
-        ++launches;
-    }
-    c->last_defer = false;
-    char what[160] = "";
-    if (c->calls.call_has_launches())
-        snprintf(what, sizeof(what), "%s, %u lists, %llu pixels, %u spp", fn, n_lists, (unsigned long long)n_entries,
-                 e->spp);
-    c->calls.end_call(what);
-    if (rc) return rc;
-    if ((rc = end_timing(c, launches))) return rc;
-    if (want_stats) {
-        if ((rc = read_aux(c, stats))) return rc;
-        return report_failure(c, "");
-    }
-    return MM_OK;
-}
-
-namespace {
-
-// Query policy of mm_query_rays / mm_trace_aov (aov_kernels.hip): the method the trace calls would take for
-// the scene and MM_OPT_TRAVERSAL (mm_plan.h choose_method), without their LDS placements -- those kernels
-// read the scene from global memory, where every grid form and both BVH forms exist.
-int aov_policy(mm_ctx* c, int& policy) {
-    if (c->pipe == MM_PIPE_REFERENCE) {
-        policy = kAovRef;
-        return MM_OK;
-    }
-    const Choice m = choose_method(scene_facts(c), plan_options(c));
-    if (m.code != MM_OK) return fail(c, m.code, m.error);
-    if (grid_form(m.form))
-        policy = kAovGrid + (grid_slow(m.form) ? kAovGridSlow : 0) + (grid_wide(m.form) ? kAovGridWide : 0) +
-                 (grid_flat(m.form) ? kAovGridFlat : 0);
-    else
-        policy = m.form == kFormLean ? kAovBvhLean : kAovBvhLi;
-    if (!aov_policy_built(policy))
-        return fail(c, MM_ERR_UNSUPPORTED, "query policy " + std::to_string(policy) + " not built");
-    return MM_OK;
-}
-
-// One numbered call of one kernel launch (a non-persistent kernel: its error flag is published into the
-// call's status word by a launch of its own).  launch(err_dev) enqueues the kernel.
-extern "C++" template <typename L>
-int enqueue_query_call(mm_ctx* c, const std::string& what, const char* name, L&& launch) {
-    int rc = begin_timing(c);
-    if (rc) return rc;
-    c->calls.begin_call();
-    rc = enqueue_launch(c, false, [&](uint32_t*, uint32_t) -> int {
-        const hipError_t le = launch(reinterpret_cast<uint32_t*>(c->d_aux + 4));
-        return le == hipSuccess ? MM_OK : fail(c, MM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(le));
-    });
-    c->calls.end_call(what);
-    if (rc) return rc;
-    return end_timing(c, 2);
-}
-
-}  // namespace
-
-int mm_query_rays(mm_ctx* c, const float* rays_dev, uint64_t n_rays, void* hits_dev) {
-    if (!c) return MM_ERR_INVALID;
-    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
-    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_query_rays: no scene uploaded");
-    if (n_rays == 0) return MM_OK;
-    if (!rays_dev || !hits_dev) return fail(c, MM_ERR_INVALID, "mm_query_rays: null argument");
-    if (reinterpret_cast<uintptr_t>(rays_dev) % 16 || reinterpret_cast<uintptr_t>(hits_dev) % 8)
-        return fail(c, MM_ERR_INVALID, "mm_query_rays: rays not 16-byte or hits not 8-byte aligned");
-    if (n_rays > aov_max_items()) return fail(c, MM_ERR_INVALID, "mm_query_rays: more rays than one launch holds");
-    HIPC(c, hipSetDevice(c->device));
-    int policy = 0;
-    if (int rc = aov_policy(c, policy)) return rc;
-    const DevScene sc = dev_scene(c);
-    char what[96];
-    snprintf(what, sizeof(what), "mm_query_rays, %llu rays", (unsigned long long)n_rays);
-    return enqueue_query_call(c, what, "launch_query_rays", [&](uint32_t* err_dev) {
-        return launch_query_rays(sc, policy, reinterpret_cast<const float4*>(rays_dev), n_rays,
-                                 reinterpret_cast<RayHit*>(hits_dev), err_dev, c->stream);
-    });
-}
-
-int mm_trace_aov(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, uint32_t n_frames, uint32_t mirror_limit,
-                 uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, const mm_aov* out) {
-    if (!c) return MM_ERR_INVALID;
-    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
-    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_aov: no scene uploaded");
-    if (!u || !out) return fail(c, MM_ERR_INVALID, "mm_trace_aov: null argument");
-    if (!out->normal_depth && !out->albedo && !out->id) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no output");
-    if (n_frames == 0) return fail(c, MM_ERR_INVALID, "mm_trace_aov: no frames");
-    if (!cams && n_frames > 1) return fail(c, MM_ERR_INVALID, "mm_trace_aov: several frames need their cameras");
-    if (int rc0 = check_tile(c, "mm_trace_aov", u, nullptr, mirror_limit, x0, y0, w, h, y_stride)) return rc0;
-    if (reinterpret_cast<uintptr_t>(out->normal_depth) % 16 || reinterpret_cast<uintptr_t>(out->albedo) % 16 ||
-        reinterpret_cast<uintptr_t>(out->id) % 4)
-        return fail(c, MM_ERR_INVALID, "mm_trace_aov: float4 outputs not 16-byte or id not 4-byte aligned");
-    const uint64_t n_pix = (uint64_t)w * h;
-    if (n_pix > 0x7FFFFFFFull || (n_pix + 255) / 256 * n_frames > 0x7FFFFFFFull)
-        return fail(c, MM_ERR_INVALID, "mm_trace_aov: more pixels than one launch holds");
-    HIPC(c, hipSetDevice(c->device));
-    int policy = 0;
-    if (int rc = aov_policy(c, policy)) return rc;
-    AovJob job;
-    job.u = *u;
-    job.cams = nullptr;
-    if (cams)
-        if (int rc = stage_cameras(c, cams, n_frames, job.cams)) return rc;
-    job.n_frames = n_frames;
-    job.mirror_limit = mirror_limit;
-    job.x0 = x0; job.y0 = y0; job.w = w; job.h = h; job.y_stride = y_stride;
-    job.normal_depth = reinterpret_cast<float4*>(out->normal_depth);
-    job.albedo = reinterpret_cast<float4*>(out->albedo);
-    job.id = out->id;
-    const DevScene sc = dev_scene(c);
-    char what[160];
-    snprintf(what, sizeof(what), "mm_trace_aov, %u frames, tile (%u, %u) %ux%u / %u, mirror limit %u", n_frames, x0,
-             y0, w, h, y_stride, mirror_limit);
-    return enqueue_query_call(c, what, "launch_trace_aov", [&](uint32_t* err_dev) {
-        return launch_trace_aov(sc, policy, job, err_dev, c->stream);
-    });
 }
 
 int mm_sync(mm_ctx* c) {

@@ -291,3 +291,32 @@ def test_errors(ragged):
     got, _ = r.trace_tile_cameras(u, rows, e, *tile)  # the context is clean again
     assert _diff(got.cpu().numpy()[1], ragged.refs[1]) == 0
     r.close()
+
+
+def test_camera_ring_wraps_at_its_full_size(gpu):
+    """Four calls of 2048 cameras each on a 4x2 tile: by the staging ring's policy (mm_stage_ring.h ring_place;
+    tests/trace_args pins this very sequence) the first call allocates 2048 records, the second grows the ring
+    to its full 4096, the third takes the upper half and the fourth finds the ring full: it waits for the
+    device and lands at record 0 again, without growing.  No sync between the last two calls; the first, a
+    middle and the last frame of each equal trace_tile with that frame's camera."""
+    from mirror_maze import default_uniform, make_ext
+
+    n, tile = 2048, (158, 88, 4, 2)
+    u = default_uniform(320, 180, 0)
+    base = _cameras(10, 320, 180, 2, 6, seed=111)
+    r = _renderer(_scene(10))
+    calls = []
+    for k in range(4):
+        cams = np.ascontiguousarray(base[(np.arange(n) + k) % len(base)])
+        cams[:, 0] += (np.arange(n) * 1e-3 + 0.37 * k).astype(np.float32)  # every record of every call its own
+        e = make_ext(8, 8, 8, frame=1000 * k)
+        calls.append((cams, e, r.trace_tile_cameras(u, cams, e, *tile)[0]))
+    r.sync()
+    assert len({c.tobytes() for cams, _, _ in calls for c in cams[[0, n // 2 - 1, n - 1]]}) == 12
+    for cams, e, out in calls[2:]:
+        out = out.cpu().numpy()
+        assert out.shape == (n, 2, 4, 4)
+        for f in (0, n // 2 - 1, n - 1):
+            one, _ = r.trace_tile(_with_cam(u, cams[f]), make_ext(8, 8, 8, frame=e.frame + f), *tile)
+            assert np.array_equal(_bits(out[f]), _bits(one.cpu().numpy())), (e.frame, f)
+    r.close()

@@ -340,7 +340,7 @@ def test_staging_bound_for_multi_frame_launches(gpu):
 
 
 def test_auto_tail_deferral_policy(gpu):
-    """MM_OPT_DEFER auto (mm_runtime.hip): the tail rings run for paths of >= 8
+    """MM_OPT_DEFER auto (mm_plan.cpp plan_tile): the tail rings run for paths of >= 8
     bounces on launches of >= 2^24 paths where the maze grid sits whole in LDS
     -- C3's 20-frame launches and rank 0's rows of an 8-way split (41 M paths)
     -- and not on a single C3 frame (16.6 M paths), for 4-bounce paths (C2) or

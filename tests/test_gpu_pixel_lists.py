@@ -513,3 +513,44 @@ def test_refine_frames_equals_refine_per_frame(maze):
     assert r.refine_frames(u, cams, e, color, var, count, float("inf"), extra, [1, 2, 3]) == [0, 0, 0]
     assert r.last_call() == calls
     r.close()
+
+
+def test_list_ring_wraps_at_its_full_size(maze):
+    """Eight calls with tables of 65535 lists (1114112 words each), nearly all of them empty: by the staging
+    ring's policy (mm_stage_ring.h ring_place) the ring grows to 1, 2 and then 4 tables (calls 1, 2 and 4: past
+    2^22 words, from where on it wraps), call 7 fills it exactly and call 8 waits for the device and takes the
+    ring's first words again, without growing.  The last two calls' entries are mm_trace_pixels' per non-empty
+    list; a table of empty lists alone takes no words and no call number."""
+    import torch
+
+    from mirror_maze import make_ext
+
+    s, u, cams, ref = maze
+    n_lists, words = 65535, (8 + 65535 + 1 + 15) // 16 * 16 + 16 * 65535
+    assert 2 * words < 2**22 <= 4 * words
+    e = make_ext(8, 8, 8, frame=90)
+    r = _renderer(s)
+    runs = []
+    for k in range(8):
+        lengths = np.zeros(n_lists, dtype=np.int64)
+        where = [0, 1, 77 + k, 32768, 65000 - 9 * k, 65534]  # the first and the last list among them
+        lengths[where] = [3, 1, 9, 8, 2 + k, 5]
+        px, offs = _lists(lengths, VIEW, seed=900 + k)
+        cams_k = np.ascontiguousarray(cams[(np.arange(n_lists) + k) % len(cams)])
+        keys_k = (np.arange(n_lists, dtype=np.uint32) * 3 + 2**20 + k)
+        calls = r.last_call()
+        out = r.trace_pixel_lists(u, cams_k, e, torch.from_numpy(px.view(np.int32)).cuda(), offs, frame_keys=keys_k)[0]
+        assert r.last_call() == calls + 1
+        runs.append((where, px, offs, cams_k, keys_k, out))
+    calls = r.last_call()
+    none = r.trace_pixel_lists(u, cams_k, e, np.zeros((0, 2), np.uint32), np.zeros(n_lists + 1, np.uint64),
+                               frame_keys=keys_k)[0]
+    assert tuple(none.shape) == (0, 4) and r.last_call() == calls  # the empty-list path: no call number
+    r.sync()
+    for where, px, offs, cams_k, keys_k, out in runs[-2:]:
+        where = sorted(where)
+        sub = np.concatenate([[0], np.cumsum([int(offs[f + 1] - offs[f]) for f in where])]).astype(np.uint64)
+        assert int(sub[-1]) == len(px)  # (the other lists are empty: the entries are these lists' back to back)
+        want, _, _, _ = _per_list(ref, u, cams_k[where], e, keys_k[where].tolist(), px, sub)
+        assert _diff(_np(out), want) == 0
+    r.close()
