@@ -93,6 +93,7 @@ struct DevGrid {
     // compiler spills those to VGPR lanes: a single-slot v_readlane per use)
     int nm1[3];
     float nf[3];               // n[a] as a float (the maze forms' end time: a kernel argument, not a hoisted convert)
+    float nm1f[3];             // n[a] - 1 as a float (the maze forms' start cell is clamped in float: grid_first_f)
 };
 // The device view of a built grid (grid_build.h) whose image was copied to `image_dev`.
 inline DevGrid dev_grid(const GridHost& gh, const uint8_t* image_dev) {
@@ -102,6 +103,7 @@ inline DevGrid dev_grid(const GridHost& gh, const uint8_t* image_dev) {
         dg.n[a] = gh.n[a];
         dg.nm1[a] = gh.n[a] - 1;
         dg.nf[a] = (float)gh.n[a];
+        dg.nm1f[a] = (float)(gh.n[a] - 1);
     }
     dg.n_glob = gh.n_glob;
     dg.slab = gh.slab ? 1u : 0u;

@@ -385,6 +385,17 @@ __device__ __forceinline__ int grid_first(const DevGrid& g, int a, float o, floa
     const int i = min(max((int)floorf((o - g.mn[a]) * g.inv[a]), 0), g.nm1[a]);
     return y > 0.0f ? i + 1 : i;
 }
+// The clamped cell index of grid_first as a float, without the integer round
+// trip: floorf gives an integer-valued float (or +-inf), and clamping it to
+// [0, n - 1] in float -- fminf(fmaxf(., 0), n - 1), as one median of three --
+// picks the same value as converting first, whose convert saturates (a NaN,
+// which no ray past the guards brings, gives 0 both ways: the convert's rule,
+// and the median's min3 rule).  The result is an exact small integer, or -0
+// (floorf(-0)): callers add 0 or 1, or convert it.
+// (tests/test_bounce_identities.py: against the integer clamp, inputs far outside the grid included.)
+__device__ __forceinline__ float grid_first_f(const DevGrid& g, int a, float o) {
+    return __builtin_amdgcn_fmed3f(floorf((o - g.mn[a]) * g.inv[a]), 0.0f, g.nm1f[a]);
+}
 
 // Search + certificate.  Returns true with (t, index) = the reference's answer
 // (t = kBig when nothing is hit), false when the caller must walk the BVH.
@@ -435,9 +446,23 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
     // further 1.3 % / 1.4 %; bit-identical; profiles/r02/ab_start_cell.txt).
     // The crossing times stay those of the origin.
     const float s0 = 0.09375f;
-    int bx = grid_first(g, 0, r.o.x + s0 * r.d.x, r.y.x),
-        by = kFlat ? (r.y.y > 0.0f ? 1 : 0) : grid_first(g, 1, r.o.y + s0 * r.d.y, r.y.y),
+    // The maze forms keep the start cell (fix, fiz) and the boundary indices
+    // (fbx, fbz: the cell index + 1 going up) in float throughout -- the walk
+    // steps float indices anyway -- and convert once, for the cell's position.
+    int bx = 0, by = kFlat ? (r.y.y > 0.0f ? 1 : 0) : 0, bz = 0;
+    float fix = 0.0f, fiz = 0.0f, fbx = 0.0f, fbz = 0.0f;
+    if constexpr (kFlat) {
+        fix = grid_first_f(g, 0, r.o.x + s0 * r.d.x);
+        fiz = grid_first_f(g, 2, r.o.z + s0 * r.d.z);
+        fbx = fix + (r.y.x > 0.0f ? 1.0f : 0.0f);  // (-0 + 0 = +0: the integer's float)
+        fbz = fiz + (r.y.z > 0.0f ? 1.0f : 0.0f);
+    } else {
+        bx = grid_first(g, 0, r.o.x + s0 * r.d.x, r.y.x);
+        by = grid_first(g, 1, r.o.y + s0 * r.d.y, r.y.y);
         bz = grid_first(g, 2, r.o.z + s0 * r.d.z, r.y.z);
+        fbx = (float)bx;
+        fbz = (float)bz;  // (exact small integers)
+    }
     // Crossing time of boundary b along axis a in one fma per step:
     // t = RN(b * B_a + A_a), A_a = RN(RN(mn_a - o_a) * y_a), B_a = RN(cell_a * y_a).
     // Its error along axis a, |dt| * |d_a|, is a few u (|mn_a - o_a| + b cell_a
@@ -447,7 +472,7 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
     const float Ax = (g.mn[0] - r.o.x) * r.y.x, Bx = g.cell[0] * r.y.x;
     const float Az = (g.mn[2] - r.o.z) * r.y.z, Bz = g.cell[2] * r.y.z;
     const float Ay = kFlat ? 0.0f : (g.mn[1] - r.o.y) * r.y.y, By = kFlat ? 0.0f : g.cell[1] * r.y.y;
-    float tx = __builtin_fmaf((float)bx, Bx, Ax), tz = __builtin_fmaf((float)bz, Bz, Az);
+    float tx = __builtin_fmaf(fbx, Bx, Ax), tz = __builtin_fmaf(fbz, Bz, Az);
     float ty = kFlat ? grid_time(g, 1, by, r.o.y, r.y.y) : __builtin_fmaf((float)by, By, Ay);
     // Cell words (grid_build.cpp).  Wide (64-bit): bits 0-21 the list's first
     // entry; bit 63 set: bits 22-31 the count, the whole list for every face;
@@ -462,7 +487,9 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
     // toward the previous cell is fixed per ray and axis), packed 8 bits per
     // axis: x, y, z.
     int ci;
-    {
+    if constexpr (kFlat) {
+        ci = (int)fiz * g.n[0] + (int)fix;
+    } else {
         const int ix = r.y.x > 0.0f ? bx - 1 : bx, iz = r.y.z > 0.0f ? bz - 1 : bz;
         const int iy = kFlat ? 0 : (r.y.y > 0.0f ? by - 1 : by);
         ci = kFlat ? iz * g.n[0] + ix : (iz * g.n[1] + iy) * g.n[0] + ix;
@@ -540,7 +567,6 @@ __device__ __forceinline__ bool grid_search(const DevGrid& g, const GV& gv, cons
         // z boundary -- the skipped cell.  tests/test_grid_stress.py counts each
         // on a float32 restatement of the two fmas.)
         const float sgx = r.y.x > 0.0f ? 1.0f : -1.0f, sgz = r.y.z > 0.0f ? 1.0f : -1.0f;
-        float fbx = (float)bx, fbz = (float)bz;  // (exact small integers)
         const float tend = fminf(ty, fminf(__builtin_fmaf(r.y.x > 0.0f ? g.nf[0] : 0.0f, Bx, Ax),
                                            __builtin_fmaf(r.y.z > 0.0f ? g.nf[2] : 0.0f, Bz, Az)));
         // (the high-half shifts of the +x / -x / +z / -z ranges: cell_pos, grid_build.cpp)

@@ -627,20 +627,32 @@ __device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, flo
     const bool hit = t < kBig;
     k = hit ? k : 0u;
     MM_LANE_STAT(kLpShade);
-    const F3 nn = xyz(sc.geo[4 * k + 1]);                    // normalize(cross(v,u)), %238
-    const float4 s0 = sc.shade[2 * k + 0];                   // color, is_mirror
-    const float sg = msign(dot3(p.dir, nn));
-    const bool lit = s0.w == 0.0f || sg == 1.0f;
+    // The records by 32-bit byte offsets from their (wave-uniform) bases: one
+    // shift per record instead of a 64-bit scaled index each (a rect index is
+    // below 2^24 + 256 -- mm_runtime.hip's node check --, so k * 64 fits).
+    const char* const geo = reinterpret_cast<const char*>(sc.geo);
+    const char* const shade = reinterpret_cast<const char*>(sc.shade);
+    const uint32_t go = k * 64u, so = k * 32u;
+    const F3 nn = xyz(*reinterpret_cast<const float4*>(geo + (go + 16u)));  // normalize(cross(v,u)), %238
+    const float4 s0 = *reinterpret_cast<const float4*>(shade + so);         // color, is_mirror
+    // dn serves the side test, the diffuse side and the mirror's reflect (its
+    // dot3(nn, dir) is the same three products summed in the same order)
+    const float dn = dot3(p.dir, nn);
+    const bool lit = s0.w == 0.0f || dn > 0.0f;              // (sign(dn) == 1 <=> dn > 0)
     const bool more = hit & (lit | (p.mh + 1 < mirror_limit));
     const bool diffuse = more & lit;
-    // Both branches end in ori += t dir, dir = normalize(X), L = contrib + L;
-    // those run once after the branch (a wave holding diffuse and mirror lanes
-    // would otherwise execute the correctly rounded 1/sqrt of each branch).
-    F3 x, contrib;
+    // Both branches end in ori += t dir, X = base + c nn, dir = normalize(X),
+    // L = contrib + L; those run once after the branch (a wave holding diffuse
+    // and mirror lanes would otherwise execute the correctly rounded 1/sqrt of
+    // each branch), and the branches leave (base, c, contrib): the diffuse
+    // rn + side nn as it stands, the mirror's dir - dd nn as dir + (-dd) nn --
+    // the same IEEE operations.
+    F3 base, contrib;
+    float cn;
     if (diffuse) {
         MM_LANE_STAT(kLpDiffuse);
-        const float side = -sg;
-        const float4 e = sc.shade[2 * k + 1];
+        const float side = -msign(dn);
+        const float4 e = *reinterpret_cast<const float4*>(shade + (so + 16u));
         contrib = (e.w * p.T) * xyz(e);                      // %253, %254
         p.T = xyz(s0) * p.T;                                 // %264
         // shaders.metal:316-318.  The path's direction samples are its RNG
@@ -685,18 +697,24 @@ __device__ __forceinline__ bool shade_step(const DevScene& sc, PathState& p, flo
         const F3 rd = F3{rx, ry, rz};
         const float len2 = dot3(rd, rd);
         const F3 rn = rsq(len2) * rd;                        // %358
-        x = rn + side * nn;                                  // %367
+        base = rn;                                           // %367: rn + side nn
+        cn = side;
     } else {
         MM_LANE_STAT(kLpMirror);
         contrib = 0.005f * xyz(s0);                          // %386
-        const float dd = dot3(nn, p.dir) * 2.0f;             // reflect, %392-%397
-        x = p.dir - dd * nn;
+        base = p.dir;                                        // reflect, %392-%397: dir - (dn 2) nn
+        cn = -(dn * 2.0f);
         p.mh += 1;
     }
+    const F3 x = base + cn * nn;
     p.ori = p.ori + t * p.dir;                               // %363
     p.dir = rsq(dot3(x, x)) * x;                             // %372 / reflect's normalize
-    const F3 l = contrib + p.L;                              // %409
-    p.L = F3{more ? l.x : p.L.x, more ? l.y : p.L.y, more ? l.z : p.L.z};
+    // L only where the path goes on -- under the lane mask (the empty asm keeps
+    // the branch): as selects the three components cost a single-slot op each
+    if (more) {
+        asm volatile("");
+        p.L = contrib + p.L;                                 // %409
+    }
     return more;
 }
 
