@@ -16,7 +16,8 @@ from ._lib import (MM_AOV_ID_FAILED, MM_AOV_ID_MIRROR_END, MM_AOV_ID_MISS, MM_AO
 from ._lib import MM_DENOISE_MAX_PASSES, MM_DN_RGBA8, mm_denoise_params  # noqa: F401
 from ._lib import MM_DNV_RGBA8, mm_denoise_var_params  # noqa: F401
 from ._lib import mm_temporal_params, mm_temporal_prev, mm_temporal_prev_var  # noqa: F401
-from .renderer import Renderer, make_ext, merge_samples, select_noisy, select_noisy_frames, select_short_history  # noqa: F401
+from .renderer import Renderer, make_ext  # noqa: F401
+from .sampling import merge_samples, select_noisy, select_noisy_frames, select_short_history  # noqa: F401
 from .scene import (ChunkScheduler, Player, Scene, calculate_quaternion, check_collision, default_uniform,  # noqa: F401
                     walk_cameras)
 

@@ -17,9 +17,17 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _args, _lib
+from ._args import tensor_ok
 from ._lib import check, lib
+from .sampling import (_select_noisy_frames, merge_at, merge_samples, select_noisy, select_noisy_frames,  # noqa: F401
+                       select_short_history)
 from .scene import Scene
+
+
+def _ptr(t, n=1):
+    """A tensor's address for a C call: None for no tensor, and for the tensors of an empty list (n = 0)."""
+    return t.data_ptr() if t is not None and n else None
 
 
 class Renderer:
@@ -57,6 +65,14 @@ class Renderer:
         self._pinned_stream = stream is not None
         handle = _lib.MM_OWN_STREAM if stream is None else int(getattr(stream, "cuda_stream", stream))
         self._check(lib().mm_set_stream(self._ctx, handle))
+
+    def _follow(self, device) -> None:
+        """Before a call that enqueues: unless a stream is pinned, take torch's current stream of `device`, so the
+        call is ordered with the torch ops that made or will read its tensors."""
+        if not self._pinned_stream:
+            import torch
+
+            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(device).cuda_stream))
 
     def own_stream(self):
         """Pin the context's own (library-created, non-blocking) stream and
@@ -137,14 +153,13 @@ class Renderer:
         RGBA CUDA tensor, with the texture-write conversion (mm_quantize_rgba8)."""
         import torch
 
-        if not (rgba.is_cuda and rgba.dtype == torch.float32 and rgba.is_contiguous() and rgba.shape[-1] == 4):
+        if not tensor_ok(rgba, torch.float32, ((..., 4),)):
             raise ValueError("rgba must be a contiguous float32 CUDA tensor [..., 4]")
         if out is None:
             out = torch.empty(rgba.shape, dtype=torch.uint8, device=rgba.device)
-        elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == rgba.shape):
+        elif not tensor_ok(out, torch.uint8, (rgba.shape,)):
             raise ValueError("out must be a contiguous uint8 CUDA tensor of rgba's shape")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(rgba.device).cuda_stream))
+        self._follow(rgba.device)
         self._check(lib().mm_quantize_rgba8(self._ctx, rgba.data_ptr(), out.data_ptr(), rgba.numel() // 4))
         return out
 
@@ -160,10 +175,17 @@ class Renderer:
         n = 1
         for d in shape:
             n *= d
-        if not (out.is_cuda and out.dtype in (torch.float32, torch.uint8) and out.is_contiguous()
-                and out.numel() == n):
+        if not tensor_ok(out, (torch.float32, torch.uint8), numel=n):
             raise ValueError(f"out must be a contiguous float32 or uint8 CUDA tensor of {n} elements")
         return out, out.dtype == torch.uint8
+
+    def _trace(self, call, ext, stats, r8, *outs):
+        """The shared end of the trace calls: `call`, the method's own C entry point, is given the references of
+        the call's ext (the caller's with the flags `stats` and `r8` ask for) and of a mm_stats.  Returns (*outs,
+        mm_stats or None)."""
+        st = _lib.mm_stats()
+        self._check(call(C.byref(_args.call_ext(ext, stats, r8)), C.byref(st)))
+        return (*outs, st if stats else None)
 
     def trace_tile(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, x0: int, y0: int, w: int, h: int,
                    y_stride: int = 1, out=None, stats: bool = False, rgba8: bool = False):
@@ -171,17 +193,10 @@ class Renderer:
         or with rgba8 / a uint8 `out` its RGBA8 texture-write conversion
         (MM_EXT_RGBA8: equal to quantize() of the float tile).  Returns (out,
         mm_stats or None)."""
-        import torch
-
         out, r8 = self._out(out, (h, w, 4), rgba8, f"cuda:{self.device}")
-        if not self._pinned_stream:  # order with the torch ops that made / read `out`
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_tile(self._ctx, C.byref(uniform), C.byref(e), x0, y0, w, h, y_stride,
-                                        out.data_ptr(), C.byref(st)))
-        return out, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_tile(self._ctx, C.byref(uniform), e, x0, y0, w, h, y_stride,
+                                                             out.data_ptr(), st), ext, stats, r8, out)
 
     def trace_tile_frames(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, n_frames: int, x0: int, y0: int,
                           w: int, h: int, y_stride: int = 1, out=None, stats: bool = False, rgba8: bool = False):
@@ -190,30 +205,13 @@ class Renderer:
         tensor (allocated if None; uint8 RGBA8 with rgba8 / a uint8 `out`, as
         trace_tile); frame f equals trace_tile with frame ext.frame + f.
         Returns (out, mm_stats summed over the frames or None)."""
-        import torch
-
         out, r8 = self._out(out, (n_frames, h, w, 4), rgba8, f"cuda:{self.device}")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_tile_frames(self._ctx, C.byref(uniform), C.byref(e), n_frames, x0, y0, w, h,
-                                               y_stride, out.data_ptr(), C.byref(st)))
-        return out, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_tile_frames(self._ctx, C.byref(uniform), e, n_frames, x0, y0,
+                                                                    w, h, y_stride, out.data_ptr(), st),
+                           ext, stats, r8, out)
 
-    @staticmethod
-    def _cameras(cameras) -> np.ndarray:
-        """(n, 10) float32 camera records (sizeof(mm_camera) = 40 B per row) from
-        an (n, 10) array or a sequence of mm_camera / mm_uniform (its .cam)."""
-        if isinstance(cameras, np.ndarray):
-            cams = np.ascontiguousarray(cameras, dtype=np.float32)
-        else:
-            rows = [np.frombuffer(bytes(getattr(c, "cam", c)), dtype=np.float32) for c in cameras]
-            cams = np.stack(rows) if rows else np.zeros((0, 10), dtype=np.float32)
-        if cams.ndim != 2 or cams.shape[1] != 10:
-            raise ValueError("cameras must be mm_camera / mm_uniform values or an (n, 10) float32 array")
-        return cams
+    _cameras = staticmethod(_args.cameras)
 
     def trace_tile_cameras(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, x0: int, y0: int,
                            w: int, h: int, y_stride: int = 1, out=None, stats: bool = False, rgba8: bool = False):
@@ -226,20 +224,14 @@ class Renderer:
         from `uniform`, its .cam is ignored.  Frame f equals trace_tile with
         uniform.cam = cameras[f] and frame ext.frame + f.  Returns (out,
         mm_stats summed over the frames or None)."""
-        import torch
-
         cams = self._cameras(cameras)
         n = cams.shape[0]
         out, r8 = self._out(out, (n, h, w, 4), rgba8, f"cuda:{self.device}")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_tile_cameras(self._ctx, C.byref(uniform), cams.ctypes.data if n else None,
-                                                C.byref(e), n, x0, y0, w, h, y_stride, out.data_ptr(),
-                                                C.byref(st)))
-        return out, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_tile_cameras(self._ctx, C.byref(uniform),
+                                                                     cams.ctypes.data if n else None, e, n, x0, y0,
+                                                                     w, h, y_stride, out.data_ptr(), st),
+                           ext, stats, r8, out)
 
     # -- closest-hit answers -------------------------------------------------
     def query_rays(self, rays, out=None):
@@ -254,17 +246,15 @@ class Renderer:
         dev = torch.device(f"cuda:{self.device}")
         if not torch.is_tensor(rays):
             rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float32)).to(dev)
-        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous() and rays.dim() == 3
-                and tuple(rays.shape[1:]) == (2, 4)):
+        if not tensor_ok(rays, torch.float32, ((None, 2, 4),)):
             raise ValueError("rays must be a contiguous float32 (n, 2, 4) CUDA tensor or array")
         n = rays.shape[0]
         if out is None:
             out = torch.empty((n, 2), dtype=torch.int32, device=rays.device)
-        elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (n, 2)):
+        elif not tensor_ok(out, torch.int32, ((n, 2),)):
             raise ValueError("out must be a contiguous int32 (n, 2) CUDA tensor")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(rays.device).cuda_stream))
-        self._check(lib().mm_query_rays(self._ctx, rays.data_ptr() if n else None, n, out.data_ptr() if n else None))
+        self._follow(rays.device)
+        self._check(lib().mm_query_rays(self._ctx, _ptr(rays, n), n, _ptr(out, n)))
         return out[:, 0].view(torch.float32), out[:, 1]
 
     AOV_NAMES = ("normal_depth", "albedo", "id")
@@ -294,11 +284,10 @@ class Renderer:
             t = (out or {}).get(k)
             if t is None:
                 t = torch.empty(shape, dtype=dt, device=dev)
-            elif not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            elif not tensor_ok(t, dt, (shape,)):
                 raise ValueError(f"out[{k!r}] must be a contiguous {dt} CUDA tensor of shape {shape}")
             bufs[k] = t
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(dev).cuda_stream))
+        self._follow(dev)
         a = _lib.mm_aov(*[bufs[k].data_ptr() if k in bufs else None for k in self.AOV_NAMES])
         self._check(lib().mm_trace_aov(self._ctx, C.byref(uniform), None if cams is None else
                                        (cams.ctypes.data if n else None), n, mirror_limit, x0, y0, w, h, y_stride,
@@ -326,8 +315,7 @@ class Renderer:
         out = self._filter_out(out, color.shape, color.device, rgba8,
                                "out must be a contiguous float32 (uint8 for RGBA8) CUDA tensor of color's shape")
         r8 = out.dtype == torch.uint8
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        self._follow(color.device)
         p = _lib.mm_denoise_params(int(n_passes), float(sigma_z), float(sigma_l), _lib.MM_DN_RGBA8 if r8 else 0)
         self._check(lib().mm_denoise_frames(self._ctx, color.data_ptr(), C.byref(a), C.byref(p), n, w, h,
                                             out.data_ptr()))
@@ -354,8 +342,8 @@ class Renderer:
         n, h, w = self._frames(color)
         lead = tuple(color.shape[:-1])
         a = self._aov_frames(aov, n, h, w, color.device, "aov")
-        if not (torch.is_tensor(var) and var.is_cuda and var.device == color.device and var.dtype == torch.float32
-                and tuple(var.shape) in (lead, (n, h, w) if n == 1 else lead, (h, w) if n == 1 else lead)):
+        if not tensor_ok(var, torch.float32, (lead, (n, h, w), (h, w)) if n == 1 else (lead,), device=color.device,
+                         contiguous=False):
             raise ValueError(f"var must be a float32 tensor of shape {lead} on {color.device}")
         if torch.is_tensor(count):
             if not (count.device == color.device and tuple(count.shape) == tuple(var.shape)):
@@ -370,14 +358,12 @@ class Renderer:
             var_out = self._filter_out(var_out, var.shape, color.device, None,
                                        "var_out must be a contiguous float32 CUDA tensor of var's shape")
         r8 = out.dtype == torch.uint8
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        self._follow(color.device)
         vmean = (var / count).to(torch.float32).contiguous()  # bookkeeping, as merge_samples is
         p = _lib.mm_denoise_var_params(int(n_passes), float(sigma_z), float(sigma_l), float(eps_l),
                                        _lib.MM_DNV_RGBA8 if r8 else 0, 0)
         self._check(lib().mm_denoise_frames_var(self._ctx, color.data_ptr(), C.byref(a), vmean.data_ptr(),
-                                                C.byref(p), n, w, h, out.data_ptr(),
-                                                None if var_out is None else var_out.data_ptr()))
+                                                C.byref(p), n, w, h, out.data_ptr(), _ptr(var_out)))
         return out if var_out is None else (out, var_out)
 
     @staticmethod
@@ -385,8 +371,7 @@ class Renderer:
         """(n, h, w) of a colour tensor, (h, w, 4) or (n, h, w, 4)."""
         import torch
 
-        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
-                and color.dim() in (3, 4) and color.shape[-1] == 4):
+        if not tensor_ok(color, torch.float32, ((None, None, 4), (None, None, None, 4))):
             raise ValueError("color must be a contiguous float32 CUDA tensor (h, w, 4) or (n, h, w, 4)")
         return (1 if color.dim() == 3 else color.shape[0]), *color.shape[-3:-1]
 
@@ -398,8 +383,7 @@ class Renderer:
         """`t`, a contiguous float32 tensor of `shape` on `device`."""
         import torch
 
-        if not (torch.is_tensor(t) and t.is_cuda and t.device == device and t.dtype == torch.float32
-                and t.is_contiguous() and tuple(t.shape) == shape):
+        if not tensor_ok(t, torch.float32, (shape,), device=device):
             raise ValueError(wording.format(what=what, shape=shape, device=device))
         return t
 
@@ -411,9 +395,8 @@ class Renderer:
 
         if out is None:
             return torch.empty(shape, dtype=torch.uint8 if rgba8 else torch.float32, device=device)
-        if not (torch.is_tensor(out) and out.is_cuda and out.device == device and out.is_contiguous()
-                and out.dtype in ((torch.float32,) if rgba8 is None else (torch.float32, torch.uint8))
-                and out.shape == shape and not (rgba8 and out.dtype != torch.uint8)):
+        dtypes = torch.float32 if rgba8 is None else torch.uint8 if rgba8 else (torch.float32, torch.uint8)
+        if not tensor_ok(out, dtypes, (shape,), device=device):
             raise ValueError(msg)
         return out
 
@@ -426,16 +409,14 @@ class Renderer:
             pc, pa, pcam, pvar = prev
         else:
             pc, pa, pcam = prev
-        if not (torch.is_tensor(pc) and pc.is_cuda and pc.device == device and pc.dtype == torch.float32
-                and pc.is_contiguous() and tuple(pc.shape) in ((h, w, 4), (1, h, w, 4))):
+        if not tensor_ok(pc, torch.float32, ((h, w, 4), (1, h, w, 4)), device=device):
             raise ValueError(f"prev's colour must be a contiguous float32 tensor of shape {(h, w, 4)} on {device}")
-        if var:
-            if not (torch.is_tensor(pvar) and tuple(pvar.shape) in ((h, w), (1, h, w))):
-                raise ValueError(f"prev's variance must be a float32 tensor of shape {(h, w)} on {device}")
-            self._plane(pvar, "prev's variance", tuple(pvar.shape), device)
-        pcam = self._cameras([pcam] if not isinstance(pcam, np.ndarray) else pcam.reshape(1, -1))
-        fields = (pc.data_ptr(), self._aov_frames(pa, 1, h, w, device, "prev's aov"),
-                  _lib.mm_camera.from_buffer_copy(pcam.tobytes()))
+        if var and not tensor_ok(pvar, torch.float32, ((h, w), (1, h, w)), device=device):
+            if torch.is_tensor(pvar) and tuple(pvar.shape) in ((h, w), (1, h, w)):  # (its shape is not what is wrong)
+                self._plane(pvar, "prev's variance", tuple(pvar.shape), device)
+            raise ValueError(f"prev's variance must be a float32 tensor of shape {(h, w)} on {device}")
+        pcam = _args.camera(pcam)
+        fields = (pc.data_ptr(), self._aov_frames(pa, 1, h, w, device, "prev's aov"), pcam)
         return _lib.mm_temporal_prev_var(*fields, pvar.data_ptr()) if var else _lib.mm_temporal_prev(*fields)
 
     @staticmethod
@@ -443,8 +424,7 @@ class Renderer:
         """(h, w) of an accumulated frame, (h, w, 4)."""
         import torch
 
-        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.is_contiguous()
-                and image.dim() == 3 and image.shape[-1] == 4):
+        if not tensor_ok(image, torch.float32, ((None, None, 4),)):
             raise ValueError("image must be a contiguous float32 (h, w, 4) CUDA tensor")
         return tuple(image.shape[:2])
 
@@ -457,8 +437,7 @@ class Renderer:
         for k in self.AOV_NAMES:
             shape, dt = ((n, h, w), torch.int32) if k == "id" else ((n, h, w, 4), torch.float32)
             t = aov[k]
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == device and t.dtype == dt and t.is_contiguous()
-                    and tuple(t.shape) in (shape, shape[1:] if n == 1 else shape)):
+            if not tensor_ok(t, dt, (shape, shape[1:]) if n == 1 else (shape,), device=device):
                 raise ValueError(f"{what}[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {device}")
         return _lib.mm_aov(*[aov[k].data_ptr() for k in self.AOV_NAMES])
 
@@ -479,8 +458,6 @@ class Renderer:
         None starts a new history.  Returns a float32 tensor of color's shape
         (`out` if given) whose alpha is the history length; it feeds denoise()
         unchanged.  The inputs are not written."""
-        import torch
-
         n, h, w = self._frames(color)
         cams = self._cameras(cameras)
         if cams.shape[0] != n:
@@ -491,8 +468,7 @@ class Renderer:
         out = self._filter_out(out, color.shape, color.device, None,
                                "out must be a contiguous float32 CUDA tensor of color's shape")
         pv = None if prev is None else self._prev(prev, h, w, color.device, False)
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        self._follow(color.device)
         p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
         self._check(lib().mm_accumulate_frames(self._ctx, C.byref(uniform), cams.ctypes.data, color.data_ptr(),
                                                C.byref(a), None if pv is None else C.byref(pv), C.byref(p), n, x0, y0,
@@ -536,12 +512,10 @@ class Renderer:
         else:
             self._plane(var_out, "var_out", lead, color.device)
         pv = None if prev is None else self._prev(prev, h, w, color.device, True)
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        self._follow(color.device)
         p = _lib.mm_temporal_params(int(n_max), float(tol_z), float(w_min), 0)
         self._check(lib().mm_accumulate_frames_var(self._ctx, C.byref(uniform), cams.ctypes.data, color.data_ptr(),
-                                                   C.byref(a), vmean.data_ptr(),
-                                                   None if weight is None else weight.data_ptr(),
+                                                   C.byref(a), vmean.data_ptr(), _ptr(weight),
                                                    None if pv is None else C.byref(pv), C.byref(p), n, x0, y0, w, h,
                                                    out.data_ptr(), var_out.data_ptr()))
         return out, var_out
@@ -549,22 +523,8 @@ class Renderer:
     # -- pixel lists -----------------------------------------------------------
     def _pixel_list(self, pixels):
         """The (n, 2) int32 CUDA tensor of a pixel list: `pixels` itself, or an
-        upload of an (n, 2) array of (x, y) pairs (int32 holds the bits of the
-        library's uint32)."""
-        import torch
-
-        dev = torch.device(f"cuda:{self.device}")
-        if not torch.is_tensor(pixels):
-            pixels = np.ascontiguousarray(pixels)
-            if pixels.dtype.kind not in "iu":
-                raise ValueError("pixels must hold integers")
-            pixels = torch.from_numpy(pixels.astype(np.uint32).view(np.int32).reshape(-1, 2)).to(dev)
-        if pixels.dtype == getattr(torch, "uint32", None):
-            pixels = pixels.view(torch.int32)
-        if not (pixels.is_cuda and pixels.dtype == torch.int32 and pixels.is_contiguous() and pixels.dim() == 2
-                and pixels.shape[1] == 2):
-            raise ValueError("pixels must be a contiguous int32 / uint32 (n, 2) CUDA tensor or an (n, 2) array")
-        return pixels
+        upload of an (n, 2) array of (x, y) pairs to this renderer's device."""
+        return _args.pixel_list(pixels, f"cuda:{self.device}")
 
     def trace_pixels(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, pixels, out=None, stats: bool = False,
                      rgba8: bool = False):
@@ -574,19 +534,12 @@ class Renderer:
         RGBA8 with rgba8 / a uint8 `out`, as trace_tile) equals pixel (x, y) of
         trace_tile with the same uniform and ext, bit for bit; an entry outside
         the view gets zeros.  Returns (out, mm_stats or None)."""
-        import torch
-
         pixels = self._pixel_list(pixels)
         n = pixels.shape[0]
         out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_pixels(self._ctx, C.byref(uniform), C.byref(e), pixels.data_ptr() if n else None,
-                                          n, out.data_ptr() if n else None, C.byref(st)))
-        return out, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_pixels(self._ctx, C.byref(uniform), e, _ptr(pixels, n), n,
+                                                               _ptr(out, n), st), ext, stats, r8, out)
 
     def blend_pixels(self, image, pixels, extra, m: float, x0: int = 0, y0: int = 0):
         """Blend extra samples into an accumulated frame, in place
@@ -596,16 +549,13 @@ class Renderer:
         returned for it; `m`: the weight of the extra samples in frames (extra
         spp / frame spp).  Entries outside the window are skipped; the list
         must not name a window pixel twice.  Returns `image`."""
-        import torch
-
         h, w = self._window(image)
         pixels = self._pixel_list(pixels)
         n = pixels.shape[0]
         self._plane(extra, "extra", (n, 4), image.device, self._ENTRIES)
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
-        self._check(lib().mm_blend_pixels(self._ctx, image.data_ptr(), x0, y0, w, h, pixels.data_ptr() if n else None,
-                                          extra.data_ptr() if n else None, n, float(m)))
+        self._follow(image.device)
+        self._check(lib().mm_blend_pixels(self._ctx, image.data_ptr(), x0, y0, w, h, _ptr(pixels, n), _ptr(extra, n),
+                                          n, float(m)))
         return image
 
     def top_up(self, uniform: _lib.mm_uniform, camera, ext: _lib.mm_ext, acc, aov, n_min: float, extra_spp: int,
@@ -628,10 +578,8 @@ class Renderer:
         if n == 0:
             return acc, 0
         u = _lib.mm_uniform.from_buffer_copy(bytes(uniform))
-        u.cam = _lib.mm_camera.from_buffer_copy(self._cameras([camera] if not isinstance(camera, np.ndarray)
-                                                              else camera.reshape(1, -1)).tobytes())
-        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
-                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        u.cam = _args.camera(camera)
+        e = _args.extra_ext(ext, extra_spp, frame_key)
         extra, _ = self.trace_pixels(u, e, pixels)
         self.blend_pixels(acc, pixels, extra, extra_spp / ext.spp, x0, y0)
         return acc, n
@@ -644,19 +592,15 @@ class Renderer:
         variance of each entry's extra MEAN (trace_pixels_var's var / extra
         spp).  The colours are blend_pixels()' bit for bit.  Returns (image,
         var)."""
-        import torch
-
         h, w = self._window(image)
         self._plane(var, "var", (h, w), image.device, self._ENTRIES)
         pixels = self._pixel_list(pixels)
         n = pixels.shape[0]
         self._plane(extra, "extra", (n, 4), image.device, self._ENTRIES)
         self._plane(extra_vmean, "extra_vmean", (n,), image.device, self._ENTRIES)
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(image.device).cuda_stream))
+        self._follow(image.device)
         self._check(lib().mm_blend_pixels_var(self._ctx, image.data_ptr(), var.data_ptr(), x0, y0, w, h,
-                                              pixels.data_ptr() if n else None, extra.data_ptr() if n else None,
-                                              extra_vmean.data_ptr() if n else None, n, float(m)))
+                                              _ptr(pixels, n), _ptr(extra, n), _ptr(extra_vmean, n), n, float(m)))
         return image, var
 
     def top_up_var(self, uniform: _lib.mm_uniform, camera, ext: _lib.mm_ext, acc, var, aov, extra_spp: int,
@@ -695,10 +639,8 @@ class Renderer:
         if n == 0:
             return acc, var, 0
         u = _lib.mm_uniform.from_buffer_copy(bytes(uniform))
-        u.cam = _lib.mm_camera.from_buffer_copy(self._cameras([camera] if not isinstance(camera, np.ndarray)
-                                                              else camera.reshape(1, -1)).tobytes())
-        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
-                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        u.cam = _args.camera(camera)
+        e = _args.extra_ext(ext, extra_spp, frame_key)
         extra, var_b, _ = self.trace_pixels_var(u, e, pixels)
         self.blend_pixels_var(acc, var, pixels, extra, (var_b / float(extra_spp)).contiguous(), extra_spp / ext.spp,
                               x0, y0)
@@ -726,17 +668,13 @@ class Renderer:
         out, r8 = self._out(out, (*lead, 4), rgba8, dev)
         if var is None:
             var = torch.zeros(lead, dtype=torch.float32, device=dev)
-        if not (var.is_cuda and var.dtype == torch.float32 and var.is_contiguous() and tuple(var.shape) == lead):
+        if not tensor_ok(var, torch.float32, (lead,)):
             raise ValueError(f"var must be a contiguous float32 CUDA tensor of shape {lead}")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_tile_var(self._ctx, C.byref(uniform), None if cams is None else cams.ctypes.data,
-                                            C.byref(e), n, x0, y0, w, h, y_stride, out.data_ptr(), var.data_ptr(),
-                                            C.byref(st)))
-        return out, var, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_tile_var(self._ctx, C.byref(uniform),
+                                                                 None if cams is None else cams.ctypes.data, e, n,
+                                                                 x0, y0, w, h, y_stride, out.data_ptr(),
+                                                                 var.data_ptr(), st), ext, stats, r8, out, var)
 
     def trace_pixels_var(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, pixels, out=None, var=None,
                          stats: bool = False, rgba8: bool = False):
@@ -751,17 +689,12 @@ class Renderer:
         out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
         if var is None:
             var = torch.zeros((n,), dtype=torch.float32, device=pixels.device)
-        if not (var.is_cuda and var.dtype == torch.float32 and var.is_contiguous() and tuple(var.shape) == (n,)):
+        if not tensor_ok(var, torch.float32, ((n,),)):
             raise ValueError(f"var must be a contiguous float32 CUDA tensor of {n} elements")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_pixels_var(self._ctx, C.byref(uniform), C.byref(e),
-                                              pixels.data_ptr() if n else None, n, out.data_ptr() if n else None,
-                                              var.data_ptr() if n else None, C.byref(st)))
-        return out, var, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_pixels_var(self._ctx, C.byref(uniform), e, _ptr(pixels, n), n,
+                                                                   _ptr(out, n), _ptr(var, n), st),
+                           ext, stats, r8, out, var)
 
     def refine(self, uniform: _lib.mm_uniform, ext: _lib.mm_ext, color, var, count, rel_tol: float, extra_spp: int,
                frame_key: int, ids=None, x0: int = 0, y0: int = 0):
@@ -784,14 +717,8 @@ class Renderer:
         n = int(pixels.shape[0])
         if n == 0:
             return 0
-        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, int(frame_key),
-                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
-        mean_b, var_b, _ = self.trace_pixels_var(uniform, e, pixels)
-        j, i = (pixels[:, 1] - y0).long(), (pixels[:, 0] - x0).long()
-        mean, v, cnt = merge_samples(color[j, i, :3], var[j, i], count[j, i], mean_b[:, :3], var_b, float(extra_spp))
-        color[j, i, :3] = mean
-        var[j, i] = v
-        count[j, i] = cnt
+        mean_b, var_b, _ = self.trace_pixels_var(uniform, _args.extra_ext(ext, extra_spp, frame_key), pixels)
+        merge_at(((pixels[:, 1] - y0).long(), (pixels[:, 0] - x0).long()), color, var, count, mean_b, var_b, extra_spp)
         return n
 
     # -- pixel lists of many frames in one launch -----------------------------------
@@ -812,38 +739,23 @@ class Renderer:
         import torch
 
         pixels = self._pixel_list(pixels)
-        offs = np.ascontiguousarray(np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets),
-                                    dtype=np.uint64).reshape(-1)
-        n_lists = offs.shape[0] - 1
-        if n_lists < 1:
-            raise ValueError("offsets must hold n_lists + 1 values, n_lists >= 1")
         n = pixels.shape[0]
-        if int(offs[-1]) != n:
-            raise ValueError(f"offsets end at {int(offs[-1])}, the pixel array holds {n} entries")
+        offs = _args.list_offsets(offsets, n)
+        n_lists = offs.shape[0] - 1
         cams = None if cameras is None else self._cameras(cameras)
         if cams is not None and cams.shape[0] != n_lists:
             raise ValueError(f"{n_lists} lists need {n_lists} cameras, not {cams.shape[0]}")
-        keys = None
-        if frame_keys is not None:
-            keys = np.ascontiguousarray(np.asarray(frame_keys), dtype=np.uint32).reshape(-1)
-            if keys.shape[0] != n_lists:
-                raise ValueError(f"{n_lists} lists need {n_lists} frame keys, not {keys.shape[0]}")
+        keys = _args.list_keys(frame_keys, n_lists)
         out, r8 = self._out(out, (n, 4), rgba8, pixels.device)
         if var is True:
             var = torch.zeros((n,), dtype=torch.float32, device=pixels.device)
-        if var is not None and not (torch.is_tensor(var) and var.is_cuda and var.dtype == torch.float32
-                                    and var.is_contiguous() and tuple(var.shape) == (n,)):
+        if var is not None and not tensor_ok(var, torch.float32, ((n,),)):
             raise ValueError(f"var must be None, True or a contiguous float32 CUDA tensor of {n} elements")
-        if not self._pinned_stream:
-            self._check(lib().mm_set_stream(self._ctx, torch.cuda.current_stream(out.device).cuda_stream))
-        e = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags | (_lib.MM_EXT_COUNT_STATS if stats else 0) | (_lib.MM_EXT_RGBA8 if r8 else 0), 0)
-        st = _lib.mm_stats()
-        self._check(lib().mm_trace_pixel_lists(
-            self._ctx, C.byref(uniform), None if cams is None else cams.ctypes.data, C.byref(e),
-            None if keys is None else keys.ctypes.data, n_lists, pixels.data_ptr() if n else None, offs.ctypes.data,
-            out.data_ptr() if n else None, var.data_ptr() if var is not None and n else None, C.byref(st)))
-        return out, var, (st if stats else None)
+        self._follow(out.device)
+        return self._trace(lambda e, st: lib().mm_trace_pixel_lists(
+            self._ctx, C.byref(uniform), None if cams is None else cams.ctypes.data, e,
+            None if keys is None else keys.ctypes.data, n_lists, _ptr(pixels, n), offs.ctypes.data, _ptr(out, n),
+            _ptr(var, n), st), ext, stats, r8, out, var)
 
     def refine_frames(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, color, var, count, rel_tol: float,
                       extra_spp: int, frame_keys, ids=None, x0: int = 0, y0: int = 0):
@@ -861,15 +773,9 @@ class Renderer:
         counts = [int(b - a) for a, b in zip(offsets[:-1], offsets[1:])]
         if int(offsets[-1]) == 0:
             return counts
-        e = _lib.mm_ext(int(extra_spp), ext.bounce_limit, ext.mirror_limit, ext.frame,
-                        ext.flags & ~(_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8 | _lib.MM_EXT_COUNT_STATS), 0)
+        e = _args.extra_ext(ext, extra_spp, ext.frame)  # (the lists' RNG frames are frame_keys)
         mean_b, var_b, _ = self.trace_pixel_lists(uniform, cameras, e, pixels, offsets, frame_keys, var=True)
-        f, j, i = fji[:, 0], fji[:, 1], fji[:, 2]
-        mean, v, cnt = merge_samples(color[f, j, i, :3], var[f, j, i], count[f, j, i], mean_b[:, :3], var_b,
-                                     float(extra_spp))
-        color[f, j, i, :3] = mean
-        var[f, j, i] = v
-        count[f, j, i] = cnt
+        merge_at(fji.unbind(1), color, var, count, mean_b, var_b, extra_spp)
         return counts
 
     def sync(self) -> None:
@@ -906,113 +812,6 @@ class Renderer:
         ms, n = C.c_float(), C.c_uint32()
         self._check(lib().mm_last_timing(self._ctx, C.byref(ms), C.byref(n)))
         return ms.value, n.value
-
-
-def select_short_history(acc, ids, n_min: float, x0: int = 0, y0: int = 0):
-    """The pixel list Renderer.top_up traces: the pixels of the accumulated
-    window `acc` ((h, w, 4), alpha = history length) with alpha < n_min whose
-    `ids` entry ((h, w) or (1, h, w) int32, the guides' id buffer) is neither
-    MM_AOV_ID_MISS nor MM_AOV_ID_FAILED, as an (n, 2) int32 tensor of (x0 + i,
-    y0 + j) pairs in row-major order (torch.nonzero's: deterministic, no
-    duplicates) on acc's device.  Works on CPU tensors too."""
-    import torch
-
-    if acc.dim() != 3 or acc.shape[-1] != 4:
-        raise ValueError("acc must be one (h, w, 4) frame")
-    ids = ids.reshape(acc.shape[:2])
-    miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)  # the int32 with those bits
-    sel = (acc[..., 3] < n_min) & (ids != miss) & (ids != failed)
-    ji = torch.nonzero(sel)  # (n, 2) rows of (j, i), row-major
-    return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
-
-
-def _lum(c):
-    """The denoiser's luminance of (..., >= 3) colours."""
-    return (0.25 * c[..., 0] + 0.5 * c[..., 1]) + 0.25 * c[..., 2]
-
-
-def select_noisy(color, var, count, rel_tol: float, floor: float = 1e-3, ids=None, x0: int = 0, y0: int = 0):
-    """The pixel list Renderer.refine traces: the pixels of the window `color`
-    ((h, w, 4) or (h, w, 3)) whose mean's standard error, sqrt(var / count), is
-    above rel_tol * (lum(color) + floor) -- `var` (h, w) as trace_tile_var
-    returns it, `count` the samples per pixel, a scalar or an (h, w) tensor;
-    `floor` keeps black pixels from being selected for ever.  With `ids` ((h, w)
-    or (1, h, w) int32, a guides' id buffer) a pixel whose id is MM_AOV_ID_MISS
-    or MM_AOV_ID_FAILED is never selected.  Returns an (n, 2) int32 tensor of
-    (x0 + i, y0 + j) pairs in row-major order (torch.nonzero's: deterministic,
-    no duplicates) on color's device.  Works on CPU tensors too."""
-    import torch
-
-    if color.dim() != 3 or color.shape[-1] < 3:
-        raise ValueError("color must be one (h, w, 4) frame")
-    var = var.reshape(color.shape[:2])
-    if torch.is_tensor(count):
-        count = count.reshape(color.shape[:2])
-    sel = torch.sqrt(var / count) > rel_tol * (_lum(color) + floor)
-    if ids is not None:
-        ids = ids.reshape(color.shape[:2])
-        miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)
-        sel = sel & (ids != miss) & (ids != failed)
-    ji = torch.nonzero(sel)
-    return torch.stack((ji[:, 1] + x0, ji[:, 0] + y0), dim=1).to(torch.int32).contiguous()
-
-
-def _select_noisy_frames(color, var, count, rel_tol, floor, ids, x0, y0):
-    """select_noisy_frames' (pixels, offsets) and the (N, 3) rows (f, j, i) of
-    the selected pixels, frame-major and row-major."""
-    import torch
-
-    if color.dim() != 4 or color.shape[-1] < 3:
-        raise ValueError("color must be (n, h, w, 4) frames")
-    lead = color.shape[:3]
-    var = var.reshape(lead)
-    if torch.is_tensor(count):
-        count = count.reshape(lead)
-    sel = torch.sqrt(var / count) > rel_tol * (_lum(color) + floor)
-    if ids is not None:
-        ids = ids.reshape(lead)
-        miss, failed = _lib.MM_AOV_ID_MISS - (1 << 32), _lib.MM_AOV_ID_FAILED - (1 << 32)
-        sel = sel & (ids != miss) & (ids != failed)
-    fji = torch.nonzero(sel)  # (N, 3) rows of (f, j, i): frame-major, then row-major
-    pixels = torch.stack((fji[:, 2] + x0, fji[:, 1] + y0), dim=1).to(torch.int32).contiguous()
-    per_frame = torch.bincount(fji[:, 0], minlength=lead[0])
-    offsets = np.zeros(lead[0] + 1, dtype=np.uint64)
-    offsets[1:] = torch.cumsum(per_frame, 0).cpu().numpy()
-    return pixels, offsets, fji
-
-
-def select_noisy_frames(color, var, count, rel_tol: float, floor: float = 1e-3, ids=None, x0: int = 0, y0: int = 0):
-    """select_noisy() for a batch of frames at once, the lists
-    Renderer.refine_frames traces: `color` (n, h, w, 4), `var` (n, h, w),
-    `count` a scalar or (n, h, w), `ids` None or the frames' id buffers.
-    Returns (pixels, offsets): the frames' select_noisy lists back to back,
-    an (N, 2) int32 tensor on color's device, and the n + 1 offsets of the
-    lists in it as a uint64 numpy array (one read-back for the whole batch),
-    as Renderer.trace_pixel_lists takes them.  Works on CPU tensors too."""
-    pixels, offsets, _ = _select_noisy_frames(color, var, count, rel_tol, floor, ids, x0, y0)
-    return pixels, offsets
-
-
-def merge_samples(mean_a, var_a, n_a, mean_b, var_b, n_b):
-    """Pool two independent groups of samples of the same pixels: `mean_*`
-    (..., 3) colours, `var_*` (...) variances of one sample's luminance as
-    trace_tile_var / trace_pixels_var return them, `n_*` the samples in each
-    group (scalars or (...) tensors).  Returns (mean, var, n) of the n_a + n_b
-    samples together:
-      mean = mean_a + (mean_b - mean_a) * n_b / (n_a + n_b)          per channel
-      var  = ((n_a-1) var_a + (n_b-1) var_b
-              + n_a n_b / (n_a+n_b) * (lum(mean_a) - lum(mean_b))**2) / (n_a + n_b - 1)
-    Plain float32 torch operations, on the tensors' device: this is bookkeeping
-    over the pixels a round selected, not on the hot path, and stays in torch."""
-    import torch
-
-    n_a = torch.as_tensor(n_a, dtype=torch.float32, device=mean_a.device)
-    n_b = torch.as_tensor(n_b, dtype=torch.float32, device=mean_a.device)
-    n = n_a + n_b
-    mean = mean_a + (mean_b - mean_a) * n_b.unsqueeze(-1) / n.unsqueeze(-1)
-    d = _lum(mean_a) - _lum(mean_b)
-    var = ((n_a - 1.0) * var_a + (n_b - 1.0) * var_b + n_a * n_b / n * d ** 2) / (n - 1.0)
-    return mean, var, n
 
 
 def make_ext(spp: int = 8, bounce_limit: int = 8, mirror_limit: int = 8, frame: int = 0,

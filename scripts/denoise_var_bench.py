@@ -77,7 +77,7 @@ def main(argv=None) -> int:
         r.sync()
         guides = _lib.mm_aov(*[aov[k].data_ptr() for k in Renderer.AOV_NAMES])
         L = _lib.lib()
-        r._check(L.mm_set_stream(r._ctx, torch.cuda.current_stream(color.device).cuda_stream))
+        r._follow(color.device)
 
         sig = inspect.signature(Renderer.denoise_var).parameters  # the sigmas are denoise_var's defaults
         sz, sl, eps = (float(sig[k].default) for k in ("sigma_z", "sigma_l", "eps_l"))
