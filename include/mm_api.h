@@ -738,7 +738,11 @@ int  mm_set_option(mm_ctx* ctx, int key, int value);
  *                            tail rings; the grid builder's budget: no grid image is built larger)
  *   MM_INFO_GRID_FLAT        1 if the grid takes the maze forms (one y cell, compact 16-byte records + class table)
  *   MM_INFO_GRID_SLAB        1 if the two global rects are a floor / ceiling pair, sorted by y, a query tests one of
- *   MM_INFO_GRID_CLASSES     threshold classes of the compact records (0 without them) */
+ *   MM_INFO_GRID_CLASSES     threshold classes of the compact records (0 without them)
+ *   MM_INFO_LAST_KERNEL_FORM the internal form of the last wave-persistent launch: 5, 7, or the grid search's
+ *                            11 plain, 12 slow, 13 wide, 14 wide + slow, 15..18 the same on a maze grid
+ *                            (MM_INFO_LAST_FORM folds 11..18 to 11); -1 before the first such launch
+ *   MM_INFO_LAST_RING        its tail-ring kind: 0 none, 1 records in global memory, 2 records in LDS */
 #define MM_INFO_GRID_OK          1
 #define MM_INFO_GRID_CELLS_X     2
 #define MM_INFO_GRID_CELLS_Y     3
@@ -760,7 +764,14 @@ int  mm_set_option(mm_ctx* ctx, int key, int value);
 #define MM_INFO_GRID_FLAT        19
 #define MM_INFO_GRID_SLAB        20
 #define MM_INFO_GRID_CLASSES     21
+#define MM_INFO_LAST_KERNEL_FORM 22
+#define MM_INFO_LAST_RING        23
 int  mm_scene_info(const mm_ctx* ctx, int key, double* value);
+
+/* Host only, no context: 1 if the build holds the wave-persistent trace kernel for this LDS mode
+ * (MM_INFO_LAST_LDS_MODE), internal form (MM_INFO_LAST_KERNEL_FORM) and tail-ring kind (MM_INFO_LAST_RING;
+ * kinds 1 and 2 exist where the pair has a tail-deferral variant), else 0. */
+int  mm_variant_built(int lds_mode, int form, int ring);
 
 /* Diagnostics: record, for every wave of the wave-persistent kernel, four u64
  * into the device buffer `dev_buf` (n_waves x 4): entry time, LDS staging

@@ -274,3 +274,10 @@ ListsPlan plan_pixel_lists(const PlanOptions& o, const mm_ext& e, const uint64_t
 }
 
 }  // namespace mm
+
+// The build's instance lists (mm_variants.h) as the C ABI tells them: ring kinds 1 and 2 where the pair has a
+// tail-deferral variant.
+extern "C" int mm_variant_built(int lds_mode, int form, int ring) {
+    if (ring == 0) return mm::wavepersist_built(lds_mode, form) ? 1 : 0;
+    return (ring == 1 || ring == 2) && mm::wavepersist_defer_built(lds_mode, form) ? 1 : 0;
+}

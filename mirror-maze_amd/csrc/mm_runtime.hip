@@ -325,6 +325,8 @@ int mm_scene_info(const mm_ctx* c, int key, double* value) {
         case MM_INFO_GRID_FLAT: *value = c->grid_ok && c->grid_flat ? 1.0 : 0.0; return MM_OK;
         case MM_INFO_GRID_SLAB: *value = c->grid_ok && g.slab && g.slab_y[0] < g.slab_y[1] ? 1.0 : 0.0; return MM_OK;
         case MM_INFO_GRID_CLASSES: *value = c->grid_ok ? c->grid_classes : 0u; return MM_OK;
+        case MM_INFO_LAST_KERNEL_FORM: *value = c->last_kern_form; return MM_OK;
+        case MM_INFO_LAST_RING: *value = c->last_kern_ring; return MM_OK;
         case MM_INFO_LAST_VGPRS:
         case MM_INFO_LAST_SCRATCH:
         case MM_INFO_LAST_STATIC_LDS: {

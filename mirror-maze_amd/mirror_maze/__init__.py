@@ -11,6 +11,7 @@ from ._lib import (MM_EXT_ACCUMULATE, MM_EXT_COUNT_STATS, MM_EXT_RGBA8, MM_INFO_
 from ._lib import (MM_INFO_GRID_LDS_CAP, MM_INFO_LAST_DEFER, MM_INFO_LAST_SCRATCH, MM_INFO_LAST_STATIC_LDS, MM_INFO_LAST_VGPRS,  # noqa: F401
                    MM_OPT_FAULT_INJECT, MM_OPT_GRID_WIDE, MM_OPT_PREDRAW, MM_OPT_PREDRAW_POOL, MM_PENDING)
 from ._lib import MM_INFO_GRID_CLASSES, MM_INFO_GRID_FLAT, MM_INFO_GRID_SLAB  # noqa: F401
+from ._lib import MM_INFO_LAST_KERNEL_FORM, MM_INFO_LAST_RING  # noqa: F401
 from ._lib import (MM_AOV_ID_FAILED, MM_AOV_ID_MIRROR_END, MM_AOV_ID_MISS, MM_AOV_ID_RECT, MM_AOV_ID_SURFACE,  # noqa: F401
                    mm_aov)
 from ._lib import MM_DENOISE_MAX_PASSES, MM_DN_RGBA8, mm_denoise_params  # noqa: F401

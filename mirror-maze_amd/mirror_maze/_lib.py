@@ -44,6 +44,7 @@ MM_INFO_GRID_GLOBAL, MM_INFO_GRID_BYTES, MM_INFO_GRID_INDEX_BYTES, MM_INFO_LEAN,
 MM_INFO_DICT_OK, MM_INFO_LAST_FORM, MM_INFO_LAST_LDS_MODE, MM_INFO_GRID_FACES = 10, 11, 12, 13
 MM_INFO_LAST_DEFER, MM_INFO_LAST_VGPRS, MM_INFO_LAST_SCRATCH, MM_INFO_LAST_STATIC_LDS = 14, 15, 16, 17
 MM_INFO_GRID_LDS_CAP, MM_INFO_GRID_FLAT, MM_INFO_GRID_SLAB, MM_INFO_GRID_CLASSES = 18, 19, 20, 21
+MM_INFO_LAST_KERNEL_FORM, MM_INFO_LAST_RING = 22, 23
 MM_PLAYER_COLLIDED, MM_PLAYER_ROTATED, MM_PLAYER_NAN_QUAT = 1, 2, 4
 MM_BVH_SWEEP, MM_BVH_EXHAUSTIVE = 0, 1
 MM_OWN_STREAM = C.c_void_p(-1 & 0xFFFFFFFFFFFFFFFF).value  # (void*)-1
@@ -172,6 +173,7 @@ EXPORTS = {
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),
+    "mm_variant_built": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mm_set_wave_timeline": (C.c_int, [P, P, C.c_uint32]),
     "mm_sync": (C.c_int, [P]),
     "mm_last_call": (C.c_int, [P, C.POINTER(C.c_uint64)]),

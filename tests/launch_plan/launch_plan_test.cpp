@@ -1,4 +1,5 @@
-// CPU driver for the launch policy (mirror-maze_amd/csrc/mm_plan.cpp): builds the maze scene of size n as
+// CPU driver for the launch policy (mirror-maze_amd/csrc/mm_plan.cpp): builds the maze scene of size n -- or,
+// with rects=PATH, the scene of a rect file (n x 12 float32: o, v, u, colour) under its own BVH -- as
 // mm_upload_scene does (BVH, compact records, grid), takes its SceneFacts, and prints the plan for the call
 // given on the command line as one JSON object.
 // Usage: launch_plan_test key=value ...   (keys below; every one has a default)
@@ -63,7 +64,38 @@ int main(int argc, char** argv) {
     }
     // the scene, and what mm_upload_scene derives from it
     mm_scene* s = nullptr;
-    if (mm_scene_build((uint32_t)arg("n", 10), 0, &s) != MM_OK) return 3;
+    mm_scene from_file{};
+    std::vector<mm_rect> file_rects;
+    std::vector<mm_node> file_nodes;
+    std::vector<uint32_t> file_idx;
+    const std::string rect_path = args("rects", "");
+    if (!rect_path.empty()) {
+        FILE* rf = fopen(rect_path.c_str(), "rb");
+        if (!rf) {
+            fprintf(stderr, "cannot read rects=%s\n", rect_path.c_str());
+            return 2;
+        }
+        mm_rect r;
+        while (fread(&r, sizeof r, 1, rf) == 1) file_rects.push_back(r);
+        fclose(rf);
+        const uint32_t n = (uint32_t)file_rects.size();
+        if (n == 0) {
+            fprintf(stderr, "no rects\n");
+            return 2;
+        }
+        file_nodes.resize(2 * (size_t)n);
+        file_idx.resize(n);
+        uint32_t n_nodes = 0;
+        if (mm_bvh_build(file_rects.data(), n, file_nodes.data(), &n_nodes, file_idx.data()) != MM_OK) return 3;
+        from_file.n_rects = n;
+        from_file.rects = file_rects.data();
+        from_file.n_nodes = n_nodes;
+        from_file.nodes = file_nodes.data();
+        from_file.idx = file_idx.data();
+        s = &from_file;
+    } else if (mm_scene_build((uint32_t)arg("n", 10), 0, &s) != MM_OK) {
+        return 3;
+    }
     uint32_t interior = 0;
     for (uint32_t i = 0; i < s->n_nodes; ++i) interior += s->nodes[i].count == 0;
     std::vector<uint32_t> recs;
@@ -129,6 +161,6 @@ int main(int argc, char** argv) {
                p.code, quoted(p.error).c_str(), p.defer, p.ring, p.fuse, p.rows_per_batch);
     }
     printf("}\n");
-    mm_scene_free(s);
+    if (s != &from_file) mm_scene_free(s);
     return 0;
 }

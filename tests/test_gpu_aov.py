@@ -54,6 +54,11 @@ def _scene(name):
             u = default_uniform(*VIEW_WIDE, 0)
         elif name == "maze64":
             s, u = Scene.build(64, 0), default_uniform(*VIEW_WIDE, 0)
+        elif name == "wide-slow-soup":
+            import variant_census_support as vc
+
+            s, u = vc.scene(vc.WIDE_SLOW_SOUP[0]), vc.uniform(vc.WIDE_SLOW_SOUP[0], 0)
+            u.view_w, u.view_h = VIEW_WIDE
         else:
             s, u = Scene.build(int(name[4:]), 0), default_uniform(*VIEW, 0)
         _CACHE[name] = (s, u)
@@ -313,6 +318,52 @@ def test_query_rays_bit_exact(gpu, ref_lib, name, policy):
         hit += int((k_ref != A.MISS).sum())
         assert ((k_ref == A.MISS) == (t_ref == np.float32(1e30))).all()
     assert hit > 500  # both answers occur
+    r.sync()
+    r.close()
+
+
+# The variant census's scenes (tests/variant_census_support.py) whose grids no other test here reads: name ->
+# (upload options, MM_INFO_* facts that pick the query policy among MM_AOV_POLICIES: grid + flat, the general
+# grid form on a maze, grid + wide + slow)
+MM_INFO_GRID_FACES, MM_INFO_GRID_FLAT = 13, 19
+CENSUS_SCENES = {
+    "maze80": ({}, {MM_INFO_GRID_FLAT: 1.0, MM_INFO_GRID_FACES: 0.0, MM_INFO_LEAN: 1.0}),
+    "maze128": ({}, {MM_INFO_GRID_FLAT: 0.0, MM_INFO_GRID_FACES: 0.0, MM_INFO_LEAN: 1.0}),
+    "wide-slow-soup": (None, {MM_INFO_GRID_FLAT: 0.0, MM_INFO_GRID_FACES: 1.0, MM_INFO_LEAN: 0.0}),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CENSUS_SCENES))
+def test_census_scenes_queries_and_aov_bit_exact(gpu, ref_lib, name):
+    """mm_query_rays (the eight ray kinds) and mm_trace_aov on N = 80 (flat, plain words, beyond N = 64's size),
+    N = 128 (a maze in the general form, coarse cells) and the census's smallest wide slow soup."""
+    opts, facts = CENSUS_SCENES[name]
+    if opts is None:
+        import variant_census_support as vc
+
+        opts = vc.WIDE_SLOW_SOUP[1]
+    s, u = _scene(name)
+    r = _renderer(s, opts)
+    assert r.scene_info(MM_INFO_GRID_OK) == 1.0
+    assert {k: r.scene_info(k) for k in facts} == facts
+    ref = _ref(ref_lib, name)
+    hit = total = 0
+    for n in (63, 4096 + 37):
+        rays = _rays(s, n, seed=100 + n)
+        t_ref, k_ref = ref.query(rays)
+        t, k = r.query_rays(rays)
+        bad = (_bits(t) != t_ref.view(np.uint32)) | (_bits(k) != k_ref)
+        assert not bad.any(), (name, n, np.flatnonzero(bad)[:8])
+        hit, total = hit + int((k_ref != A.MISS).sum()), total + n
+    assert 0.05 * total < hit < 0.95 * total, (hit, total)  # both answers occur (the soup is sparse: 333 hits)
+    seen = set()
+    for tile in (TILES if u.view_w == VIEW[0] else WIDE_TILES):
+        for limit in (1, 15):
+            tref = _ref_tile(ref_lib, name, u, limit, tile)
+            d = _diffs(_trace(r, u, limit, tile), tref)
+            assert not any(d.values()), (name, tile, limit, d)
+            seen |= {int(x) for x in np.unique(np.minimum(tref["id"] >> 30, 3))}
+    assert 1 in seen, seen  # surfaces were compared
     r.sync()
     r.close()
 

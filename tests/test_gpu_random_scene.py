@@ -46,9 +46,10 @@ def random_scene(n, seed, lattice):
 # method is unavailable (form 7 needs a compact record for every rect -- the fine
 # scene's rects have normals that are not exactly +-1, SLOW records -- and the
 # nodes + records in LDS: the BVH's 192 KB of nodes exceed the LDS budget, so
-# loop form 5 reads them through L1/L2, mode 0).
+# loop form 5 reads them through L1/L2, mode 0).  The grid images of 3000 rects
+# (239 KB / 216 KB) exceed the static LDS array: the index alone is staged, mode 12.
 CASES = {
-    "auto-grid": ({}, {False: (11, (11, 12)), True: (11, (11, 12))}),
+    "auto-grid": ({}, {False: (11, (12,)), True: (11, (12,))}),
     "bvh-lean": ({7: 7}, {False: None, True: None}),
     "bvh-li": ({7: 5}, {False: (5, (0,)), True: (5, (0,))}),
     "grid-global": ({7: 11, 1: 0}, {False: (11, (13,)), True: (11, (13,))}),
@@ -58,8 +59,8 @@ CASES = {
 @pytest.mark.parametrize("lattice", [False, True], ids=["fine", "lattice"])
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_random_scene_windows_bit_exact(gpu, lattice, case):
-    from mirror_maze import (MM_INFO_GRID_OK, MM_INFO_LAST_FORM, MM_INFO_LAST_LDS_MODE, MM_INFO_LEAN, MMError,
-                             Renderer, default_uniform, make_ext)
+    from mirror_maze import (MM_INFO_GRID_OK, MM_INFO_LAST_FORM, MM_INFO_LAST_KERNEL_FORM, MM_INFO_LAST_LDS_MODE,
+                             MM_INFO_LAST_RING, MM_INFO_LEAN, MMError, Renderer, default_uniform, make_ext)
     from oracle.oracle import Oracle
 
     opts, expect = CASES[case]
@@ -86,6 +87,9 @@ def test_random_scene_windows_bit_exact(gpu, lattice, case):
         assert (st.rays, st.paths) == (rst.rays, rst.paths)
     assert r.scene_info(MM_INFO_LAST_FORM) == expect[0]
     assert r.scene_info(MM_INFO_LAST_LDS_MODE) in expect[1]
+    # the internal form: the fine soup's SLOW records take the slow grid form
+    assert r.scene_info(MM_INFO_LAST_KERNEL_FORM) == (expect[0] if expect[0] != 11 else 11 if lattice else 12)
+    assert r.scene_info(MM_INFO_LAST_RING) == 0.0
     r.close()
 
 
