@@ -623,6 +623,98 @@ int  mm_blend_pixels_var(mm_ctx* ctx, float* image_dev, float* var_dev,
                          uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const uint32_t* pixels_dev,
                          const float* extra_dev, const float* extra_vmean_dev, uint64_t n_pixels, float m);
 
+/* Frames traced on a pixel lattice, rebuilt at full resolution from the AOVs.
+ *
+ * primary_dir maps pixel px to the screen point vx*px/view_w - vx/2, with no
+ * half-pixel offset, so for s a power of two pixel (X, Y) of the view
+ * (view_w/s, view_h/s) looks along the direction of pixel (sX, sY) of the full
+ * view, bit for bit: a frame traced at 1/s of the view IS the full frame's
+ * lattice of every s-th pixel, and the full-resolution guides at the lattice
+ * pixels are its guides.  This call interpolates the lattice's colours to every
+ * pixel of the window, across one surface only (also a surface seen in a
+ * mirror), and marks the pixels no lattice neighbour can stand in for: holes,
+ * which mm_trace_pixel_lists and mm_fill_pixels then fill.
+ *
+ * s = p->scale; lw = ceil(w/s), lh = ceil(h/s).  low_dev: n_frames*lw*lh float4,
+ * frame-major; element (X, Y) is the traced value of window pixel (sX, sY) --
+ * mm_trace_tile / _frames / _cameras / _var with the view (view_w/s, view_h/s)
+ * and the tile (x0/s, y0/s, lw, lh), where x0, y0 and the view size are
+ * multiples of s.  The call itself works in window index space, as
+ * mm_denoise_frames does.  guides: the three full-resolution buffers of one
+ * mm_trace_aov call over (w, h), all required.  low_vmean_dev: n_frames*lw*lh
+ * floats, the variance of the lattice pixels' MEAN luminance, or NULL (then
+ * var_out_dev must be NULL); given without var_out_dev it is checked and not
+ * read.  out_dev: n_frames*w*h float4; weight_out_dev and
+ * var_out_dev: n_frames*w*h floats, or NULL.
+ *
+ * All arithmetic is IEEE binary32, no contraction, in the order written;
+ * subnormals are kept and / is correctly rounded.  L is low_dev, VL
+ * low_vmean_dev, nd / al / id the guides.  For pixel p = (x, y) of frame f:
+ *   X0 = x / s; Y0 = y / s                                   (integers)
+ *   a = (float)(x - s*X0) * (1.0f / (float)s);  b = (float)(y - s*Y0) * (1.0f / (float)s)
+ *   HOLE: out = (0,0,0,0); weight = 0; var = 0
+ *   if id_p == MM_AOV_ID_FAILED: HOLE
+ *   S = (0,0,0); W = 0; G2 = 0; SV = 0
+ *   for (dx,dy) in (0,0), (1,0), (0,1), (1,1):
+ *     Q = (X0+dx, Y0+dy); skip Q outside [0,lw) x [0,lh)
+ *     g = (dx ? a : 1.0f - a) * (dy ? b : 1.0f - b); skip unless g > 0
+ *     q = window pixel (s*Q.x, s*Q.y)
+ *     skip unless id_q == id_p (all 32 bits) and al_q.w == al_p.w
+ *            and (nd_p.x*nd_q.x + nd_p.y*nd_q.y) + nd_p.z*nd_q.z >= 0
+ *     S.c = S.c + g * L_Q.c (c = r,g,b);  W = W + g;  G2 = G2 + g*g;  SV = SV + (g*g) * VL_Q
+ *   unless W >= w_min: HOLE
+ *   out = (S.r / W, S.g / W, S.b / W, 1.0f);  weight = (W*W) / G2;  var = SV / (W*W)
+ * There is no depth term: one planar rect seen through the same mirrors from
+ * the same side is the whole test (a soft depth term made more holes and a
+ * worse frame, DESIGN.md s4 "Tracing a lattice and rebuilding from the AOVs").
+ * A lattice pixel has one tap with g = 1: it returns its traced value, its
+ * variance and weight 1 on all bits.  weight is the pixel's effective sample
+ * weight in frames, in [1, 4], what mm_accumulate_frames_var takes as
+ * weight_dev once the holes are filled; 0 marks a hole.  var is EXACT for the
+ * noise part: the taps are distinct lattice pixels with independent samples
+ * (unlike mm_denoise_frames_var's Vout and mm_accumulate_frames_var's, whose
+ * taps share ancestors); what it leaves out is the interpolation's own error.
+ *
+ * MM_ERR_INVALID, in this order: a null low_dev, guides, p or out_dev, or a
+ * null guide buffer; scale not 2, 4 or 8; w_min outside (0, 1] (a NaN counts
+ * as outside); flags or reserved not 0; w, h or n_frames 0; a pointer that is
+ * not aligned (float4: 16 bytes; id, variances and weights: 4); var_out_dev
+ * given without low_vmean_dev; w*h above 2^31 - 1, n_frames*w*h above 2^40 or
+ * n_frames * ceil(w/64) * ceil(h/4) above 2^26 - 1 (one launch's blocks); an
+ * output overlapping an input; two outputs overlapping.  None of the checks
+ * needs the context; a null context is refused last.  Enqueued on the
+ * context's stream, ONE launch for all frames; the inputs are never written;
+ * the call keeps no scratch and needs no uploaded scene. */
+int  mm_upsample_frames(mm_ctx* ctx, const float* low_dev, const mm_aov* guides,
+                        const float* low_vmean_dev, const mm_upsample_params* p,
+                        uint32_t n_frames, uint32_t w, uint32_t h,
+                        void* out_dev, float* weight_out_dev, float* var_out_dev);
+
+/* Replace the pixels of a list in a window's images, in place: what fills
+ * mm_upsample_frames' holes with traced pixels.  image_dev, the window,
+ * pixels_dev, extra_dev, n_pixels: as mm_blend_pixels_var; var_dev and
+ * weight_dev: w*h floats each (4-byte aligned), or NULL; extra_vmean_dev:
+ * n_pixels floats, given exactly when var_dev is.  For an entry e inside the
+ * window, at pixel p:
+ *   image[p] = extra[e]  (all four floats);  var[p] = extra_vmean[e];  weight[p] = m
+ * each where its buffer is given: copies, exact on all bits.  (mm_blend_pixels
+ * cannot do this: with A.a = 0 it computes (E*m)/m, which is not E on all
+ * bits.)  The skip rule, the duplicate rule and n_pixels = 0 are
+ * mm_blend_pixels': entries outside the window touch nothing, the list must
+ * not name a window pixel twice, and an empty list returns MM_OK without a
+ * look at the list's buffers.
+ * MM_ERR_INVALID, in this order: a null image_dev; an empty window or more
+ * than 2^31 - 1 pixels; m not positive and finite; a misaligned image_dev,
+ * var_dev or weight_dev; two of those overlapping; then, for n_pixels > 0: a
+ * null pixels_dev or extra_dev; var_dev without extra_vmean_dev or the
+ * reverse; a misaligned list buffer (float4: 16 bytes, the list: 8,
+ * variances: 4); n_pixels above 2^38; a list buffer overlapping image_dev,
+ * var_dev or weight_dev.  A null context is refused last. */
+int  mm_fill_pixels(mm_ctx* ctx, float* image_dev, float* var_dev, float* weight_dev,
+                    uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                    const uint32_t* pixels_dev, const float* extra_dev,
+                    const float* extra_vmean_dev, uint64_t n_pixels, float m);
+
 /* Pipeline selection for mm_trace_tile (MM_PIPE_AUTO picks the fastest). */
 #define MM_PIPE_AUTO       0
 #define MM_PIPE_MEGAKERNEL 1   /* bounce loop in-kernel (MM_OPT_PERSIST picks the kernel) */
@@ -703,6 +795,11 @@ int  mm_set_pipeline(mm_ctx* ctx, int pipe);
                                   pooled, the further trials of the paths whose windows hold fewer accepted
                                   trials than the path reads (cross-lane permutes; mm_trace.h pool_trials);
                                   0 own rounds only.  Results never depend on it */
+#define MM_OPT_UPSAMPLE_LDS 29 /* mm_upsample_frames: 1 (default) a block stages its lattice footprint (at most
+                                  33 x 3 pixels) in LDS and the taps read it there; 0 the taps gather the
+                                  lattice from global memory.  The same arithmetic on the same values; staging
+                                  measured 0.78 (scale 2) and 0.87 (scale 4) of the gathers' time
+                                  (profiles/upsample/ab.txt) */
 #define MM_OPT_FAULT_INJECT 23 /* tests of the error path (results are then invalid): 0 off (default); 1 every
                                   wave-persistent launch raises an injected fault (error bit 3); 2 the tail
                                   rings' protocol waits give up at once (bit 2 when a wait was needed; a

@@ -143,6 +143,15 @@ typedef struct mm_temporal_prev_var { /* 80 bytes: mm_temporal_prev for mm_accum
     const float* var;     /* DEVICE, w*h floats: that frame's var_out of the earlier call */
 } mm_temporal_prev_var;
 
+/* Parameters of mm_upsample_frames (mm_api.h): frames traced on the lattice of
+ * every scale-th pixel, rebuilt at full resolution from the mm_aov buffers. */
+typedef struct mm_upsample_params {   /* 16 bytes */
+    uint32_t scale;     /* 2, 4 or 8: the lattice holds window pixels (scale*X, scale*Y) */
+    float    w_min;     /* in (0, 1]: least sum of valid bilinear weights that counts; below it the pixel is a hole */
+    uint32_t flags;     /* 0 */
+    uint32_t reserved;  /* 0 */
+} mm_upsample_params;
+
 /* Return codes (0 = success; never panics or throws across the ABI). */
 #define MM_OK               0
 #define MM_ERR_INVALID     -1  /* bad argument / shape                        */

@@ -117,6 +117,7 @@ struct mm_ctx {
     mm::CallTracker calls;
     int opt_predraw = -1;        // MM_OPT_PREDRAW: trials pre-drawn per path at a chunk's start (-1: by the bounce limit)
     bool opt_predraw_pool = true;  // MM_OPT_PREDRAW_POOL: pooled top-up rounds after the pre-pass's own rounds
+    bool opt_upsample_lds = true;  // MM_OPT_UPSAMPLE_LDS: mm_upsample_frames stages its lattice footprint in LDS
     int opt_fault = 0;           // MM_OPT_FAULT_INJECT
     bool opt_grid_merge = true;  // MM_OPT_GRID_MERGE (read by mm_upload_scene)
     int opt_grid_cell = 100;     // MM_OPT_GRID_CELL (read by mm_upload_scene)

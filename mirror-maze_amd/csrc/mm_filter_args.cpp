@@ -154,4 +154,69 @@ ArgCheck check_blend(bool var, const char* name, const float* image, const float
     return {};
 }
 
+ArgCheck check_upsample(const char* name, const float* low, const mm_aov* guides, const float* low_vmean,
+                        const mm_upsample_params* p, uint32_t n_frames, uint32_t w, uint32_t h, const void* out,
+                        const float* weight_out, const float* var_out) {
+    if (!p || !guides || !low || !out) return bad(name, "null argument");
+    if (!guides->normal_depth || !guides->albedo || !guides->id)
+        return bad(name, "all three guide buffers are required");
+    if (p->scale != 2 && p->scale != 4 && p->scale != 8) return bad(name, "scale must be 2, 4 or 8");
+    if (!(p->w_min > 0.0f && p->w_min <= 1.0f)) return bad(name, "w_min must be in (0, 1]");
+    if (p->flags) return bad(name, "unknown flags");
+    if (p->reserved != 0) return bad(name, "reserved must be 0");
+    if (w == 0 || h == 0 || n_frames == 0) return bad(name, "empty tile or no frames");
+    // (the byte counts: as in check_denoise.  The lattice's buffers hold ceil(w / scale) x ceil(h / scale) pixels.)
+    const uint64_t n_pix = (uint64_t)w * h, n_all = n_pix * n_frames;
+    const uint64_t n_low = (((uint64_t)w + p->scale - 1) / p->scale) * (((uint64_t)h + p->scale - 1) / p->scale) * n_frames;
+    const FilterBuf bufs[] = {{low, n_low * 16, 16, false},
+                              {guides->normal_depth, n_all * 16, 16, false},
+                              {guides->albedo, n_all * 16, 16, false},
+                              {guides->id, n_all * 4, 4, false},
+                              {low_vmean, n_low * 4, 4, false},
+                              {out, n_all * 16, 16, true},
+                              {weight_out, n_all * 4, 4, true},
+                              {var_out, n_all * 4, 4, true}};
+    const size_t n_bufs = sizeof bufs / sizeof bufs[0];
+    if (any_misaligned(bufs, n_bufs))
+        return bad(name, "misaligned buffer (float4: 16 bytes; id, variances and weights: 4)");
+    if (var_out && !low_vmean) return bad(name, "var_out_dev needs low_vmean_dev");
+    if (too_many_pixels(n_pix, n_frames)) return bad(name, "more pixels than one call holds");
+    if (upsample_blocks(w, h, n_frames) > kUpsampleMaxBlocks) return bad(name, "more blocks than one launch holds");
+    if (output_hits_input(bufs, n_bufs)) return bad(name, "an output overlaps an input");
+    if (outputs_overlap(bufs, n_bufs)) return bad(name, "two outputs overlap");
+    return {};
+}
+
+ArgCheck check_fill(const char* name, const float* image, const float* var_image, const float* weight_image,
+                    uint32_t w, uint32_t h, const uint32_t* pixels, const float* extra, const float* extra_vmean,
+                    uint64_t n_pixels, float m) {
+    if (!image) return bad(name, "null image");
+    const uint64_t n_pix = (uint64_t)w * h;
+    if (w == 0 || h == 0 || n_pix > 0x7FFFFFFFull) return bad(name, "empty window or more than 2^31 - 1 pixels");
+    if (!(m > 0.0f) || !std::isfinite(m)) return bad(name, "m must be positive and finite");
+    // the window's images are written in place: outputs, which no input may touch
+    const FilterBuf window[] = {{image, n_pix * 16, 16, true},
+                                {var_image, n_pix * 4, 4, true},
+                                {weight_image, n_pix * 4, 4, true}};
+    if (any_misaligned(window, 3)) return bad(name, "misaligned image, variance or weight");
+    if (outputs_overlap(window, 3)) return bad(name, "two of image_dev, var_dev and weight_dev overlap");
+    if (n_pixels == 0) return {};
+    if (!pixels || !extra) return bad(name, "null argument");
+    if ((var_image != nullptr) != (extra_vmean != nullptr))
+        return bad(name, "var_dev and extra_vmean_dev go together");
+    // one image of the window, then the list's buffers (their byte counts: once n_pixels has passed its bound)
+    FilterBuf t[] = {window[0],
+                     {extra, n_pixels * 16, 16, false},
+                     {pixels, n_pixels * 8, 8, false},
+                     {extra_vmean, n_pixels * 4, 4, false}};
+    if (any_misaligned(t + 1, 3)) return bad(name, "misaligned buffer (float4: 16 bytes, the list: 8, variances: 4)");
+    if (n_pixels > (1ull << 38)) return bad(name, "more entries than one launch holds");
+    if (output_hits_input(t, 4)) return bad(name, "an input overlaps the image");
+    t[0] = window[1];
+    if (output_hits_input(t, 4)) return bad(name, "an input overlaps var_dev");
+    t[0] = window[2];
+    if (output_hits_input(t, 4)) return bad(name, "an input overlaps weight_dev");
+    return {};
+}
+
 }  // namespace mm

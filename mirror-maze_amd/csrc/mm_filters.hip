@@ -1,7 +1,7 @@
 // mm_filters.hip — the frame filters of the C ABI (include/mm_api.h): mm_denoise_frames, mm_accumulate_frames,
-// mm_blend_pixels and their _var forms.  One implementation per pair: the variance call is the plain call with
-// more buffers, and what it adds stands under `var`.  A plain call's parameter and history structs are widened
-// to the variance call's at the entry point.
+// mm_blend_pixels and their _var forms, mm_upsample_frames and mm_fill_pixels.  One implementation per pair: the
+// variance call is the plain call with more buffers, and what it adds stands under `var`.  A plain call's
+// parameter and history structs are widened to the variance call's at the entry point.
 //
 // Every call checks its arguments first (mm_filter_args.h), and none of the checks needs the context: a binding
 // can be tested without a GPU, and a null context is refused only after them.
@@ -219,6 +219,57 @@ int mm_blend_pixels_var(mm_ctx* c, float* image_dev, float* var_dev, uint32_t x0
                         uint64_t n_pixels, float m) {
     return blend_impl(c, true, "mm_blend_pixels_var", image_dev, var_dev, x0, y0, w, h, pixels_dev, extra_dev,
                       extra_vmean_dev, n_pixels, m);
+}
+
+int mm_upsample_frames(mm_ctx* c, const float* low_dev, const mm_aov* guides, const float* low_vmean_dev,
+                       const mm_upsample_params* p, uint32_t n_frames, uint32_t w, uint32_t h, void* out_dev,
+                       float* weight_out_dev, float* var_out_dev) {
+    const ArgCheck ck = check_upsample("mm_upsample_frames", low_dev, guides, low_vmean_dev, p, n_frames, w, h, out_dev,
+                                       weight_out_dev, var_out_dev);
+    if (ck.code != MM_OK) return fail(c, ck.code, ck.error);
+    if (!c) return MM_ERR_INVALID;
+    HIPC(c, hipSetDevice(c->device));
+    UpFrames a;
+    a.low = reinterpret_cast<const float4*>(low_dev);
+    a.vlow = low_vmean_dev;
+    a.nd = reinterpret_cast<const float4*>(guides->normal_depth);
+    a.al = reinterpret_cast<const float4*>(guides->albedo);
+    a.id = guides->id;
+    a.out = reinterpret_cast<float4*>(out_dev);
+    a.wout = weight_out_dev;
+    a.vout = var_out_dev;
+    a.w = w; a.h = h;
+    a.lw = (w + p->scale - 1) / p->scale; a.lh = (h + p->scale - 1) / p->scale;  // (w, h < 2^31: no overflow)
+    a.n_frames = n_frames;
+    a.shift = p->scale == 2 ? 1u : p->scale == 4 ? 2u : 3u;
+    a.inv_s = 1.0f / (float)p->scale;
+    a.w_min = p->w_min;
+    a.lds = c->opt_upsample_lds;
+    HIPC(c, launch_upsample_frames(a, c->stream));
+    return MM_OK;
+}
+
+int mm_fill_pixels(mm_ctx* c, float* image_dev, float* var_dev, float* weight_dev, uint32_t x0, uint32_t y0, uint32_t w,
+                   uint32_t h, const uint32_t* pixels_dev, const float* extra_dev, const float* extra_vmean_dev,
+                   uint64_t n_pixels, float m) {
+    const ArgCheck ck = check_fill("mm_fill_pixels", image_dev, var_dev, weight_dev, w, h, pixels_dev, extra_dev,
+                                   extra_vmean_dev, n_pixels, m);
+    if (ck.code != MM_OK) return fail(c, ck.code, ck.error);
+    if (!c) return MM_ERR_INVALID;
+    if (n_pixels == 0) return MM_OK;
+    HIPC(c, hipSetDevice(c->device));
+    UpFill b;
+    b.image = reinterpret_cast<float4*>(image_dev);
+    b.var = var_dev;
+    b.weight = weight_dev;
+    b.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+    b.extra = reinterpret_cast<const float4*>(extra_dev);
+    b.extra_vmean = extra_vmean_dev;
+    b.n = n_pixels;
+    b.x0 = x0; b.y0 = y0; b.w = w; b.h = h;
+    b.m = m;
+    HIPC(c, launch_fill_pixels(b, c->stream));
+    return MM_OK;
 }
 
 }  // extern "C"

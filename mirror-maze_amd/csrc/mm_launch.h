@@ -1,5 +1,5 @@
-// mm_launch.h — host-callable launchers for the kernels in trace_kernels.hip, display.hip, denoise_kernels.hip
-// and temporal_kernels.hip, and the argument structs they take.
+// mm_launch.h — host-callable launchers for the kernels in trace_kernels.hip, display.hip, denoise_kernels.hip,
+// temporal_kernels.hip and upsample_kernels.hip, and the argument structs they take.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -256,6 +256,42 @@ struct TpBlendVar {
     const float* extra_vmean = nullptr; // n entries: the variance of the extra samples' mean
 };
 hipError_t launch_blend_pixels_var(const TpBlendVar& blend, hipStream_t s);
+
+// mm_upsample_frames (upsample_kernels.hip): all frames of one call.  Frame f's full-resolution buffers start at
+// element f * w * h, its lattice buffers at f * lw * lh.
+struct UpFrames {
+    const float4* low = nullptr;     // the lattice's traced colours
+    const float* vlow = nullptr;     // the lattice's variances of the pixel mean; read only with vout
+    const float4* nd = nullptr;      // full-resolution guides
+    const float4* al = nullptr;
+    const uint32_t* id = nullptr;
+    float4* out = nullptr;
+    float* wout = nullptr;           // nullptr: no weight output (own kernel)
+    float* vout = nullptr;           // nullptr: no variance output (own kernel); set only with vlow
+    uint32_t w = 0, h = 0, lw = 0, lh = 0;  // w * h < 2^31; lw = ceil(w / scale), lh = ceil(h / scale)
+    uint32_t n_frames = 0;
+    uint32_t shift = 1;              // log2(scale): 1, 2 or 3
+    uint32_t tiles_x = 0, tiles = 0; // set by the launcher: 64 x 4 tiles per row / per frame
+    float inv_s = 0.5f;              // 1.0f / (float)scale (exact)
+    float w_min = 0.0f;
+    bool lds = true;                 // MM_OPT_UPSAMPLE_LDS: stage the block's lattice footprint in LDS (else: gathers)
+};
+// (hipErrorInvalidValue for more blocks than one launch holds: check_upsample's bound, mm_filter_args.h)
+hipError_t launch_upsample_frames(const UpFrames& frames, hipStream_t s);
+
+// mm_fill_pixels (upsample_kernels.hip): n list entries replace their pixels of the window's images.
+struct UpFill {
+    float4* image = nullptr;         // the window's w * h pixels
+    float* var = nullptr;            // its variances; nullptr: none (then extra_vmean is nullptr too)
+    float* weight = nullptr;         // its weights; nullptr: none
+    const uint2* pixels = nullptr;   // n entries (x, y), view coordinates
+    const float4* extra = nullptr;   // n entries: the traced pixels
+    const float* extra_vmean = nullptr;
+    uint64_t n = 0;                  // (n + 255) / 256 < 2^31
+    uint32_t x0 = 0, y0 = 0, w = 0, h = 0;  // w * h < 2^31
+    float m = 0.0f;                  // what weight[p] becomes
+};
+hipError_t launch_fill_pixels(const UpFill& fill, hipStream_t s);
 
 // Per-pixel reduction of spp samples in the reference's order, then / spp.
 hipError_t launch_resolve(const TileJob& job, const Sample* samples, void* out, hipStream_t s);

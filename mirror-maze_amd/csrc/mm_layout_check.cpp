@@ -41,5 +41,8 @@ static_assert(sizeof(mm_temporal_prev) == 72 && offsetof(mm_temporal_prev, guide
 static_assert(sizeof(mm_temporal_prev_var) == 80 && offsetof(mm_temporal_prev_var, guides) == 8 &&
                   offsetof(mm_temporal_prev_var, cam) == 32 && offsetof(mm_temporal_prev_var, var) == 72,
               "mm_temporal_prev_var is mm_temporal_prev and a pointer");
+static_assert(sizeof(mm_upsample_params) == 16 && offsetof(mm_upsample_params, w_min) == 4 &&
+                  offsetof(mm_upsample_params, flags) == 8 && offsetof(mm_upsample_params, reserved) == 12,
+              "mm_upsample_params is four 4-byte fields");
 
 extern "C" int mm_layout_ok(void) { return 1; }

@@ -294,6 +294,10 @@ int mm_set_option(mm_ctx* c, int key, int value) {
             if (value < 0 || value > 1) return fail(c, MM_ERR_INVALID, "pre-pass pooling must be 0 or 1");
             c->opt_predraw_pool = value != 0;
             return MM_OK;
+        case MM_OPT_UPSAMPLE_LDS:
+            if (value < 0 || value > 1) return fail(c, MM_ERR_INVALID, "upsample LDS staging must be 0 or 1");
+            c->opt_upsample_lds = value != 0;
+            return MM_OK;
         case MM_OPT_FAULT_INJECT:
             if (value < 0 || value > 4) return fail(c, MM_ERR_INVALID, "fault inject must be 0..4");
             c->opt_fault = value;

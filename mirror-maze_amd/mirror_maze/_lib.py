@@ -36,7 +36,7 @@ MM_PIPE_AUTO, MM_PIPE_MEGAKERNEL, MM_PIPE_WAVEFRONT, MM_PIPE_REFERENCE = 0, 1, 2
 MM_OPT_LDS_NODES, MM_OPT_BLOCK, MM_OPT_PERSIST, MM_OPT_TRAVERSAL, MM_OPT_LDS_RECTS = 1, 2, 3, 7, 8
 MM_OPT_LDS_SPLIT, MM_OPT_FUSE_RESOLVE, MM_OPT_RESERVE_CUS, MM_OPT_DICT_NODES, MM_OPT_DEFER = 9, 12, 19, 20, 21
 MM_OPT_DEFER_MIN, MM_OPT_FAULT_INJECT, MM_OPT_GRID_MERGE, MM_OPT_GRID_CELL = 22, 23, 24, 25
-MM_OPT_GRID_WIDE, MM_OPT_PREDRAW, MM_OPT_PREDRAW_POOL = 26, 27, 28
+MM_OPT_GRID_WIDE, MM_OPT_PREDRAW, MM_OPT_PREDRAW_POOL, MM_OPT_UPSAMPLE_LDS = 26, 27, 28, 29
 MM_PENDING = 1
 MM_TRAV_AUTO, MM_TRAV_IFIF, MM_TRAV_LEAF_INTERIOR, MM_TRAV_LEAN, MM_TRAV_GRID = -1, 0, 5, 7, 11
 MM_INFO_GRID_OK, MM_INFO_GRID_CELLS_X, MM_INFO_GRID_CELLS_Y, MM_INFO_GRID_CELLS_Z = 1, 2, 3, 4
@@ -107,6 +107,10 @@ class mm_temporal_prev_var(C.Structure):
     _fields_ = [("color", C.c_void_p), ("guides", mm_aov), ("cam", mm_camera), ("var", C.c_void_p)]
 
 
+class mm_upsample_params(C.Structure):
+    _fields_ = [("scale", C.c_uint32), ("w_min", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class mm_rng(C.Structure):
     _fields_ = [("key", C.c_uint32 * 8), ("counter", C.c_uint64), ("buf", C.c_uint32 * 64), ("pos", C.c_uint32)]
 
@@ -170,6 +174,10 @@ EXPORTS = {
                                       C.POINTER(mm_stats)]),
     "mm_trace_pixel_lists": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), P, C.c_uint32, P, P, P, P,
                                        C.POINTER(mm_stats)]),
+    "mm_upsample_frames": (C.c_int, [P, P, C.POINTER(mm_aov), P, C.POINTER(mm_upsample_params), C.c_uint32, C.c_uint32,
+                                     C.c_uint32, P, P, P]),
+    "mm_fill_pixels": (C.c_int, [P, P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, C.c_uint64,
+                                 C.c_float]),
     "mm_set_pipeline": (C.c_int, [P, C.c_int]),
     "mm_set_option": (C.c_int, [P, C.c_int, C.c_int]),
     "mm_scene_info": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),

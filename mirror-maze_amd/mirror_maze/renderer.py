@@ -20,8 +20,8 @@ import numpy as np
 from . import _args, _lib
 from ._args import tensor_ok
 from ._lib import check, lib
-from .sampling import (_select_noisy_frames, merge_at, merge_samples, select_noisy, select_noisy_frames,  # noqa: F401
-                       select_short_history)
+from .sampling import (_select_noisy_frames, merge_at, merge_samples, select_holes, select_holes_frames,  # noqa: F401
+                       select_noisy, select_noisy_frames, select_short_history)
 from .scene import Scene
 
 
@@ -777,6 +777,171 @@ class Renderer:
         mean_b, var_b, _ = self.trace_pixel_lists(uniform, cameras, e, pixels, offsets, frame_keys, var=True)
         merge_at(fji.unbind(1), color, var, count, mean_b, var_b, extra_spp)
         return counts
+
+    # -- tracing a lattice and rebuilding from the AOVs ---------------------------------
+    def upsample(self, low, aov, scale: int, w_min: float = 0.25, low_vmean=None, want_weight: bool = True,
+                 out=None):
+        """Rebuild full-resolution frames from frames traced on the lattice of
+        every scale-th pixel (mm_upsample_frames).  `low`: an (lh, lw, 4) or (n,
+        lh, lw, 4) float32 CUDA tensor, lw = ceil(w / scale) and lh = ceil(h /
+        scale): element (Y, X) is the traced value of window pixel (scale * X,
+        scale * Y), what trace_tile* returns for the view (view_w / scale,
+        view_h / scale) and the tile (x0 / scale, y0 / scale, lw, lh).  `aov`:
+        the dict trace_aov returns for the full-resolution window (w, h) and the
+        same cameras, all three buffers.  A pixel is interpolated from those of
+        the four lattice pixels around it that show its surface through the same
+        mirrors from the same side; where their bilinear weights sum to less
+        than `w_min` (or the guides failed) it is a hole: zeros, weight 0.
+        `low_vmean`: None, or the variance of the lattice pixels' MEAN luminance
+        (trace_tile_var's var / spp), low's shape without the last axis.
+        Returns (color, weight, var): color of the aov's frames' shape + (4,)
+        (`out` if given), alpha 1; weight (None unless want_weight) the pixel's
+        effective sample weight in frames, 1 at lattice pixels, up to 4 between
+        them, 0 at holes -- accumulate_var's `weight` once the holes are filled;
+        var (None without low_vmean) the variance of color's luminance, exact
+        for the noise part.  `out`: None, or the float32 tensor the colour is
+        written to (as denoise()'s).  The inputs are not written."""
+        import torch
+
+        n, lh, lw = self._frames(low)
+        if int(scale) not in (2, 4, 8):
+            raise ValueError("scale must be 2, 4 or 8")
+        s = int(scale)
+        ids = aov.get("id") if isinstance(aov, dict) else None
+        if not torch.is_tensor(ids) or ids.dim() < 2:
+            raise ValueError(f"aov must hold the buffers {self.AOV_NAMES} of trace_aov")
+        h, w = ids.shape[-2:]
+        if (-(-w // s), -(-h // s)) != (lw, lh):
+            raise ValueError(f"a {w} x {h} window at scale {s} needs a {-(-w // s)} x {-(-h // s)} lattice, not {lw} x {lh}")
+        a = self._aov_frames(aov, n, h, w, low.device, "aov")
+        lead = tuple(low.shape[:-3]) + (h, w)
+        if low_vmean is not None:
+            self._plane(low_vmean, "low_vmean", tuple(low.shape[:-1]), low.device)
+        out = self._filter_out(out, (*lead, 4), low.device, None,
+                               "out must be a contiguous float32 CUDA tensor of the full-resolution frames' shape")
+        weight = torch.empty(lead, dtype=torch.float32, device=low.device) if want_weight else None
+        var = None if low_vmean is None else torch.empty(lead, dtype=torch.float32, device=low.device)
+        self._follow(low.device)
+        p = _lib.mm_upsample_params(s, float(w_min), 0, 0)
+        self._check(lib().mm_upsample_frames(self._ctx, low.data_ptr(), C.byref(a), _ptr(low_vmean), C.byref(p), n, w, h,
+                                             out.data_ptr(), _ptr(weight), _ptr(var)))
+        return out, weight, var
+
+    def fill_pixels(self, image, pixels, extra, m: float = 1.0, var=None, extra_vmean=None, weight=None,
+                    x0: int = 0, y0: int = 0):
+        """Replace the pixels of a list in a window's images, in place
+        (mm_fill_pixels): image[p] = extra[e], and where given var[p] =
+        extra_vmean[e] and weight[p] = m, copies exact on all bits.  `image`:
+        the (h, w, 4) float32 CUDA tensor of the window (x0, y0, w, h);
+        `pixels`, `extra`: a pixel list and what trace_pixels returned for it;
+        `var`, `weight`: (h, w) float32 or None; `extra_vmean`: (n,) float32,
+        given exactly when `var` is.  Entries outside the window are skipped;
+        the list must not name a window pixel twice.  Returns `image`."""
+        h, w = self._window(image)
+        if (var is None) != (extra_vmean is None):
+            raise ValueError("var and extra_vmean go together")
+        pixels = self._pixel_list(pixels)
+        n = pixels.shape[0]
+        self._plane(extra, "extra", (n, 4), image.device, self._ENTRIES)
+        if var is not None:
+            self._plane(var, "var", (h, w), image.device, self._ENTRIES)
+            self._plane(extra_vmean, "extra_vmean", (n,), image.device, self._ENTRIES)
+        if weight is not None:
+            self._plane(weight, "weight", (h, w), image.device, self._ENTRIES)
+        self._follow(image.device)
+        self._check(lib().mm_fill_pixels(self._ctx, image.data_ptr(), _ptr(var), _ptr(weight), x0, y0, w, h,
+                                         _ptr(pixels, n), _ptr(extra, n), _ptr(extra_vmean, n), n, float(m)))
+        return image
+
+    def _low_var(self, ulow, cams, ext, x0, y0, w, h):
+        """trace_upsampled's low view with its variance, (n, h, w, 4) and (n, h, w): one trace_tile_var launch for
+        all cameras where the library takes it (a camera sequence is a multi-frame launch even with one camera, and
+        a multi-frame variance launch needs the tail rings: MM_ERR_UNSUPPORTED below MM_OPT_DEFER_MIN paths,
+        refused before anything is enqueued), else one single-frame call per camera -- the camera in the uniform,
+        RNG frame ext.frame + f -- whose frame is the launch's bit for bit."""
+        import torch
+
+        n = cams.shape[0]
+        if n > 1:
+            try:
+                low, lvar, _ = self.trace_tile_var(ulow, ext, x0, y0, w, h, cameras=cams)
+                return low, lvar
+            except _lib.MMError as err:
+                if err.code != _lib.MM_ERR_UNSUPPORTED:
+                    raise
+        dev = f"cuda:{self.device}"
+        low = torch.empty((n, h, w, 4), dtype=torch.float32, device=dev)
+        lvar = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+        for f in range(n):
+            uf = _lib.mm_uniform.from_buffer_copy(bytes(ulow))
+            uf.cam = _args.camera(cams[f])
+            ef = _lib.mm_ext(ext.spp, ext.bounce_limit, ext.mirror_limit, ext.frame + f, ext.flags, 0)
+            self.trace_tile_var(uf, ef, x0, y0, w, h, out=low[f], var=lvar[f])
+        return low, lvar
+
+    def trace_upsampled(self, uniform: _lib.mm_uniform, cameras, ext: _lib.mm_ext, scale: int, x0: int, y0: int,
+                        w: int, h: int, mirror_limit=None, w_min: float = 0.25, var: bool = False, fill: bool = True):
+        """A camera sequence traced on the lattice of every scale-th pixel and
+        rebuilt from the AOVs: the window (x0, y0, w, h) of uniform's view, one
+        frame per camera (what trace_tile_cameras takes).  x0, y0 and the view
+        size must be multiples of `scale`.  The steps:
+          * the low view (view_w / scale, view_h / scale), tile (x0 / scale, y0
+            / scale, ceil(w / scale), ceil(h / scale)), by trace_tile_cameras --
+            with `var` by trace_tile_var, whose variance / ext.spp travels on:
+            in one launch where a multi-frame variance launch runs (at least
+            MM_OPT_DEFER_MIN paths, the tail rings), else one single-frame
+            call per camera, which runs at any size and gives the same bits;
+          * trace_aov of the full-resolution window (`mirror_limit`: None takes
+            ext.mirror_limit);
+          * upsample();
+          * with `fill`, ONE trace_pixel_lists call over the holes of all
+            frames -- the full view, list f's camera cameras[f] and RNG frame
+            ext.frame + f, so a filled pixel equals that pixel of trace_tile on
+            the full view bit for bit -- and one fill_pixels call per frame
+            with m = 1.
+        Returns (color (n, h, w, 4), aov, weight (n, h, w), var (n, h, w) or
+        None, hole share per frame: a list of n floats, holes / (w * h) before
+        the fill).  color, weight and var feed accumulate_var and denoise_var
+        (count 1) unchanged once the holes are filled.
+        RNG streams: a low-view pixel's stream is keyed by its index in the low
+        view, so it coincides with the stream of an unrelated full-view pixel
+        whose index is equal (a filled hole may share its stream with a lattice
+        pixel elsewhere in the frame).  It correlates no neighbours."""
+        s = int(scale)
+        if s not in (2, 4, 8):
+            raise ValueError("scale must be 2, 4 or 8")
+        vw, vh = int(uniform.view_w), int(uniform.view_h)
+        if vw != uniform.view_w or vh != uniform.view_h or any(v % s for v in (vw, vh, x0, y0)):
+            raise ValueError(f"x0, y0 and the view size must be multiples of scale {s}")
+        if ext.flags & (_lib.MM_EXT_ACCUMULATE | _lib.MM_EXT_RGBA8):
+            raise ValueError("trace_upsampled takes a plain float frame: no MM_EXT_ACCUMULATE, no MM_EXT_RGBA8")
+        cams = self._cameras(cameras)
+        n = cams.shape[0]
+        ulow = _lib.mm_uniform.from_buffer_copy(bytes(uniform))
+        ulow.view_w, ulow.view_h = float(vw // s), float(vh // s)
+        lw, lh = -(-w // s), -(-h // s)
+        low_vmean = None
+        if var:
+            low, lvar = self._low_var(ulow, cams, ext, x0 // s, y0 // s, lw, lh)
+            low_vmean = (lvar / float(ext.spp)).contiguous()
+        else:
+            low, _ = self.trace_tile_cameras(ulow, cams, ext, x0 // s, y0 // s, lw, lh)
+        aov = self.trace_aov(uniform, cams, ext.mirror_limit if mirror_limit is None else mirror_limit,
+                             x0=x0, y0=y0, w=w, h=h)
+        color, weight, vout = self.upsample(low, aov, s, w_min, low_vmean)
+        pixels, offsets = select_holes_frames(weight, x0, y0)
+        share = [float(b - a) / float(w * h) for a, b in zip(offsets[:-1], offsets[1:])]
+        if fill and int(offsets[-1]) > 0:
+            e = _args.extra_ext(ext, ext.spp, ext.frame)
+            extra, evar, _ = self.trace_pixel_lists(uniform, cams, e, pixels, offsets, var=True if var else None)
+            evm = None if evar is None else (evar / float(ext.spp)).contiguous()
+            for f in range(n):
+                a, b = int(offsets[f]), int(offsets[f + 1])
+                if a == b:
+                    continue
+                self.fill_pixels(color[f], pixels[a:b], extra[a:b], 1.0, None if vout is None else vout[f],
+                                 None if evm is None else evm[a:b], weight[f], x0, y0)
+        return color, aov, weight, vout, share
 
     def sync(self) -> None:
         """Wait for this context's work; raises MMError for the oldest

@@ -1,6 +1,7 @@
-"""The torch bookkeeping around the extra-sample rounds of Renderer.top_up / refine: which pixels a round
-traces (select_*) and how its samples are pooled with the ones a pixel holds (merge_samples).  Plain torch
-operations on the tensors' device, CPU tensors included; no Renderer and no library."""
+"""The torch bookkeeping around the extra-sample rounds of Renderer.top_up / refine and the hole filling of
+Renderer.trace_upsampled: which pixels a round traces (select_*) and how its samples are pooled with the ones a
+pixel holds (merge_samples).  Plain torch operations on the tensors' device, CPU tensors included; no Renderer and
+no library."""
 from __future__ import annotations
 
 import numpy as np
@@ -91,6 +92,33 @@ def select_noisy_frames(color, var, count, rel_tol: float, floor: float = 1e-3, 
     lists in it as a uint64 numpy array (one read-back for the whole batch),
     as Renderer.trace_pixel_lists takes them.  Works on CPU tensors too."""
     pixels, offsets, _ = _select_noisy_frames(color, var, count, rel_tol, floor, ids, x0, y0)
+    return pixels, offsets
+
+
+def select_holes(weight, x0: int = 0, y0: int = 0):
+    """The holes of ONE upsampled frame: the pixels of `weight` ((h, w), what
+    Renderer.upsample returns beside the colour) that are 0, as an (n, 2) int32
+    tensor of (x0 + i, y0 + j) pairs in row-major order (torch.nonzero's:
+    deterministic, no duplicates) on weight's device.  Works on CPU tensors
+    too."""
+    if weight.dim() != 2:
+        raise ValueError("weight must be one (h, w) frame")
+    return _listed(weight == 0, x0, y0)[1]
+
+
+def select_holes_frames(weight, x0: int = 0, y0: int = 0):
+    """select_holes() for a batch of frames at once: `weight` (n, h, w).
+    Returns (pixels, offsets) in select_noisy_frames' form -- the frames' lists
+    back to back as an (N, 2) int32 tensor and their n + 1 offsets as a uint64
+    numpy array (one read-back for the whole batch) -- as
+    Renderer.trace_pixel_lists takes them.  Works on CPU tensors too."""
+    import torch
+
+    if weight.dim() != 3:
+        raise ValueError("weight must be (n, h, w) frames")
+    fji, pixels = _listed(weight == 0, x0, y0)
+    offsets = np.zeros(weight.shape[0] + 1, dtype=np.uint64)
+    offsets[1:] = torch.cumsum(torch.bincount(fji[:, 0], minlength=weight.shape[0]), 0).cpu().numpy()
     return pixels, offsets
 
 

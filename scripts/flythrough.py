@@ -15,6 +15,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate     # + frame_NNNN_acc.png beside each frame
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate --top-up 2:24   # + extra samples where the history is short
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate-var --denoise-var   # + frame_NNNN_accv.png, and the variance-guided filter on it
+    python scripts/flythrough.py --maze 32 --frames 40 --upsample 2 --denoise          # trace every 2nd pixel, rebuild from the AOVs: frame_NNNN_up.png
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
@@ -79,6 +80,19 @@ mm_blend_pixels_var, SPP at least 2, RNG frame 2^21 + f) and with --refine (ever
 frame is refined first and enters with weight = count / --spp per pixel and
 vmean = var / count).
 
+--upsample S[:W_MIN] (S = 2, 4 or 8; --width and --height multiples of S) traces
+only the lattice of every S-th pixel -- the view (width / S, height / S) -- and
+rebuilds the frames from the full-resolution feature buffers through
+Renderer.trace_upsampled (mm_upsample_frames; the pixels no lattice neighbour can
+stand in for are traced in one mm_trace_pixel_lists launch per batch and filled
+by mm_fill_pixels).  It writes frame_NNNN_up.png instead of frame_NNNN.png and
+prints the share of holes per frame.  It composes with --denoise, with
+--denoise-var (the rebuilt frame's variance, count 1) and with --accumulate-var
+(the rebuilt pixels' effective sample weight and variance are passed on); with
+either of the last two the lattice is traced with its variance -- in one launch
+where a multi-frame variance launch runs, else frame by frame.
+Not with --accumulate, --refine or --top-up.
+
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
 """
@@ -137,6 +151,10 @@ def main(argv=None) -> int:
     ap.add_argument("--refine", metavar="TOL[:SPP[:ROUNDS]]", default=None,
                     help="also write frame_NNNN_ref.png: up to ROUNDS (default 2) rounds of SPP more samples (default "
                          "3 x --spp) for the pixels whose standard error is above TOL times their luminance")
+    ap.add_argument("--upsample", metavar="S[:W_MIN]", default=None,
+                    help="trace the lattice of every S-th pixel (S = 2, 4 or 8) and rebuild the frames from the feature "
+                         "buffers (Renderer.trace_upsampled): writes frame_NNNN_up.png; composes with --denoise, "
+                         "--denoise-var and --accumulate-var")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
@@ -176,6 +194,20 @@ def main(argv=None) -> int:
         if not (refine[0] > 0.0 and 2 <= refine[1] <= 4096 and 1 <= refine[2] <= 64 and a.spp >= 2):
             ap.error("--refine: TOL must be positive, SPP in 2..4096, ROUNDS in 1..64, and --spp at least 2")
 
+    upsample = None  # (scale, w_min)
+    if a.upsample is not None:
+        if a.accumulate or a.refine is not None or a.top_up is not None:
+            ap.error("--upsample does not go with --accumulate, --refine or --top-up")
+        try:
+            scale, _, w_min = a.upsample.partition(":")
+            upsample = (int(scale), float(w_min) if w_min else 0.25)
+        except ValueError:
+            ap.error("--upsample takes S[:W_MIN]")
+        if upsample[0] not in (2, 4, 8) or not 0.0 < upsample[1] <= 1.0:
+            ap.error("--upsample: S must be 2, 4 or 8 and W_MIN in (0, 1]")
+        if a.width % upsample[0] or a.height % upsample[0]:
+            ap.error("--upsample: --width and --height must be multiples of S")
+
     from mirror_maze import Player, Scene, walk_cameras
 
     scene = Scene.build(a.maze, a.seed)
@@ -197,7 +229,7 @@ def main(argv=None) -> int:
     out_dir.mkdir(parents=True, exist_ok=True)
     u = player.uniform()  # view size and chunk width; its camera is not used
     with_var = refine is not None or a.denoise_var or a.accumulate_var  # the frames are traced with their per-pixel sample variance
-    floats = a.denoise or a.accumulate or with_var  # the batch is traced as float frames
+    floats = a.denoise or a.accumulate or with_var or upsample is not None  # the batch is traced as float frames
     prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera (-var: and its variance)
     with Renderer(0) as r:
         r.upload_scene(scene)
@@ -208,14 +240,25 @@ def main(argv=None) -> int:
             # stages, and the tail deferral such a launch needs (from MM_OPT_DEFER_MIN's 2^24 paths on, where the
             # plan has it; the call refuses the launch otherwise, before anything is enqueued)
             paths = len(batch) * a.width * a.height * a.spp
-            one_var_launch = (a.accumulate_var or refine is not None) and len(batch) > 1 and 2**24 <= paths <= 2**29
+            one_var_launch = ((a.accumulate_var or refine is not None) and len(batch) > 1 and 2**24 <= paths <= 2**29
+                              and not upsample)
             if one_var_launch:
                 try:
                     img, var, _ = r.trace_tile_var(u, e, 0, 0, a.width, a.height, cameras=batch)
                     count = torch.full_like(var, float(a.spp))
                 except MMError:
                     one_var_launch = False
-            if one_var_launch:
+            up_bufs = up_weight = None
+            if upsample:
+                # the lattice, the feature buffers, the rebuilt frames and their filled holes: one launch per stage for
+                # the batch (with a variance the lattice frame by frame where a multi-frame variance launch does not run)
+                img, up_bufs, up_weight, var, share = r.trace_upsampled(u, batch, e, upsample[0], 0, 0, a.width,
+                                                                        a.height, w_min=upsample[1], var=with_var)
+                count = 1.0  # var is already the variance of the rebuilt pixel's mean
+                for k in range(len(batch)):
+                    print(f"# frame {f0 + k}: upsampled x{upsample[0]}, holes {100.0 * share[k]:.2f} % "
+                          f"(traced at full resolution and filled)", flush=True)
+            elif one_var_launch:
                 pass
             elif with_var:
                 # frame by frame (a single-frame variance call runs at any size; frame k is the batch launch's)
@@ -231,10 +274,11 @@ def main(argv=None) -> int:
                 img, _ = r.trace_tile_cameras(u, batch, e, 0, 0, a.width, a.height, rgba8=not floats)
             frames = (r.quantize(img) if floats else img).cpu().numpy()
             r.sync()
+            tag = "_up" if upsample else ""
             for k in range(len(batch)):
-                write_png(out_dir / f"frame_{f0 + k:04d}.png", frames[k])
+                write_png(out_dir / f"frame_{f0 + k:04d}{tag}.png", frames[k])
             print(f"# frames {f0}..{f0 + len(batch) - 1}: {'one launch each' if with_var and not one_var_launch else 'one launch'}, "
-                  f"{out_dir}/frame_{f0:04d}.png ...", flush=True)
+                  f"{out_dir}/frame_{f0:04d}{tag}.png ...", flush=True)
             if refine:
                 # the whole batch per round: one selection, one list launch (mm_trace_pixel_lists), one merge.  A
                 # frame that selects nothing in a round selects nothing in the later ones either: its rounds end
@@ -257,8 +301,8 @@ def main(argv=None) -> int:
                     write_png(out_dir / f"frame_{f0 + k:04d}_ref.png", done[k])
             if a.aov is None and not (a.denoise or a.denoise_var or a.accumulate or a.accumulate_var):
                 continue
-            bufs = r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
-                               want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
+            bufs = up_bufs or r.trace_aov(u, batch, a.mirrors, x0=0, y0=0, w=a.width, h=a.height,
+                                          want=Renderer.AOV_NAMES if floats else ("normal_depth", "id"))
             if a.accumulate and top_up:
                 # frame by frame: the history of frame k is the topped-up frame k - 1
                 acc_img = torch.empty_like(img)
@@ -276,6 +320,8 @@ def main(argv=None) -> int:
             if a.accumulate_var:
                 vmean = (var / count).contiguous()  # the variance of each frame's pixel mean
                 weight = (count / float(a.spp)).contiguous() if refine else None  # refined pixels hold more samples
+                if upsample:
+                    weight = up_weight  # a rebuilt pixel's effective sample weight, 1 where it was traced
                 if top_up:
                     # frame by frame: the history of frame k is the topped-up frame k - 1
                     acc_img, acc_var = torch.empty_like(img), torch.empty_like(var)
