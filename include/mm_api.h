@@ -548,6 +548,74 @@ int  mm_trace_pixel_lists(mm_ctx* ctx, const mm_uniform* uni, const mm_camera* c
                           const uint32_t* pixels_dev, const uint64_t* offsets,
                           void* out_dev, float* var_dev, mm_stats* stats);
 
+/* ---- radiance along caller-supplied rays ------------------------------------------
+ * The trace calls above start every path at uni->cam.center along a pinhole
+ * camera's primary direction; mm_query_rays takes any ray but returns only its
+ * first hit.  mm_trace_rays answers "what radiance arrives along this ray":
+ * the shaded, averaged value of the path statement for each ray of a list, in
+ * one launch (plus the resolve launch when the samples are staged) -- other
+ * cameras (equirectangular, orthographic, fisheye, stereo), light probes,
+ * radiance leaving a point of a wall, one path replayed for debugging.  There
+ * is no uni: no camera and no view.
+ *
+ * rays_dev: DEVICE pointer, 16-byte aligned, 8 words per ray:
+ * (ox, oy, oz, key, dx, dy, dz, -), mm_query_rays' record.  Word 3 is read as
+ * a uint32_t RNG key (its bit pattern, not a float conversion); word 7 is
+ * ignored.  Stream-ordered -- the caller keeps the buffer unchanged until the
+ * call has finished, the context makes no copy.  Any ray mm_query_rays allows
+ * is allowed: origins outside the scene or on a wall, unnormalised directions,
+ * zero components.  ray_flags: 0 or MM_RAYS_JITTER.
+ *
+ * Sample s (0 .. spp-1) of entry e runs the path statement of
+ * src/shaders.metal:302-344 (the bounce loop every trace call runs) with
+ *   ori  = (ox, oy, oz)
+ *   seed = the throughput-mode seed of (pixel = key, sample = s, ext->frame),
+ *          the function mm_trace_tile applies to pixel y*view_w + x
+ *   dir  = (dx, dy, dz) as given, no random number drawn before the first
+ *          bounce; with MM_RAYS_JITTER, d + (j1*0.001f, j2*0.001f, 0.0f*0.001f)
+ *          where j1, j2 are the seed's first two draws: the primary ray's
+ *          jitter exactly (a dz of -0.0f becomes +0.0f, as -0.0f + 0.0f is)
+ * and ext->bounce_limit / ext->mirror_limit.  The sample's value is
+ * sqrt(max(L, 0)) as in every trace call.
+ *
+ * out_dev: n_rays float4 (16-byte aligned), or 4-byte RGBA8 pixels with
+ * MM_EXT_RGBA8.  out[e] is the mean of entry e's spp sample values in the
+ * resolve's order T (mm_trace_tile_var above), divided by (float)spp, alpha 1:
+ * what mm_trace_tile defines for a pixel.  MM_EXT_RGBA8, MM_EXT_ACCUMULATE and
+ * MM_EXT_COUNT_STATS behave exactly as in mm_trace_pixels (stats: rays and
+ * paths exact).  Duplicate records get equal results, each in its own element.
+ * var_dev: NULL, or n_rays floats (4-byte aligned, not overlapping out_dev):
+ * mm_trace_pixels_var's variance per entry under that call's conditions
+ * (spp >= 2, no MM_EXT_ACCUMULATE, the samples always staged); out is the same
+ * with and without it.
+ *
+ * Equivalence: with MM_RAYS_JITTER and, for each pixel (x, y) of a list, the
+ * record (uni->cam.center, y*view_w + x, primary direction of (x, y) under
+ * uni), out equals mm_trace_pixels' -- and var mm_trace_pixels_var's -- for
+ * the pixel list (x, y) on all bits.
+ *
+ * n_rays = 0: MM_OK, nothing enqueued, no call number taken.  MM_ERR_INVALID,
+ * the first that applies: a null ext, rays_dev or out_dev; a misaligned
+ * rays_dev or out_dev; unknown ray_flags; spp or the limits out of range (as
+ * in mm_trace_tile); MM_EXT_RGBA8 with MM_EXT_ACCUMULATE; with var_dev, that
+ * call's conditions (spp < 2, MM_EXT_ACCUMULATE, a misaligned var_dev, var_dev
+ * overlapping out_dev); n_rays * spp (in chunks padded to 64) beyond the
+ * launch's 32-bit queue; more than 2^29 staged paths when the samples are
+ * staged (64 % spp != 0, MM_OPT_FUSE_RESOLVE 0, MM_PIPE_REFERENCE or var_dev);
+ * a null context.  MM_ERR_NO_SCENE without a scene; an earlier failed call is
+ * reported first.  MM_PIPE_WAVEFRONT: MM_ERR_UNSUPPORTED (the launch never
+ * runs the mirror-tail rings: MM_OPT_DEFER and MM_OPT_DEFER_MIN select nothing
+ * and MM_INFO_LAST_DEFER reads 0 after it); MM_PIPE_REFERENCE runs the
+ * one-thread-per-path kernel.  A traversal-stack overflow is reported as
+ * MM_ERR_STACK, as in the tile calls.  Enqueued on the context's stream,
+ * numbered and timed like the other trace calls (mm_last_timing counts 1 or 2
+ * launches); the call tracker names it mm_trace_rays with the ray count and
+ * spp. */
+#define MM_RAYS_JITTER 0x1u
+int  mm_trace_rays(mm_ctx* ctx, const mm_ext* ext, uint32_t ray_flags,
+                   const float* rays_dev, uint64_t n_rays,
+                   void* out_dev, float* var_dev, mm_stats* stats);
+
 /* ---- variance through the history ----------------------------------------------
  * mm_accumulate_frames with the variance of the pixel mean carried beside the
  * colour, and a weight per pixel and frame: the accumulated frame then has

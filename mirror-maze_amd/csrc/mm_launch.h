@@ -51,6 +51,8 @@ struct TileJob {
     // wave_ts: every other member keeps the offset it had without it.)
     // 2: the pixel lists of several frames in one launch (mm_trace_pixel_lists): `lists` below is the launch's
     // list table, which names the pixels.
+    // 3 (kListRays): a ray-list launch (mm_trace_rays): `rays` below holds the paths' origins, directions and
+    // RNG keys; no pixel is named, so the resolves take the tile path (w = n_rays, h = 1).
     uint32_t list = 0;
     // Diagnostics (mm_set_wave_timeline): per wave of the wave-persistent
     // kernel, 4 x u64 = (entry, LDS staged, exit, chunks) in wall_clock64()
@@ -74,6 +76,10 @@ struct TileJob {
     TailQueue tail;
     // 1: the rings' records in LDS (the kRing = 2 kernel, where the grid image leaves room); 0: in `tail`
     uint32_t ring_lds = 0;
+    // Ray list (mm_trace_rays, `list` == kListRays): MM_RAYS_JITTER -- the record's direction gets the primary
+    // ray's jitter (the seed's first two draws) before the first bounce.  Launch-uniform; read by the kList == 3
+    // instances only.  (In the padding ahead of `status`: every other member keeps its offset.)
+    uint32_t ray_jitter = 0;
     // Per-launch status word (host-mapped pinned memory, mm_runtime.hip): the
     // last wave of the launch moves the error flag into it, | kStatusDone, so
     // the host attributes an error to the call that launched it without a
@@ -115,12 +121,19 @@ struct TileJob {
     // Pixel lists of several frames (mm_trace_pixel_lists, `list` == 2): the slot points at the launch's list
     // table (ListTable below) -- the pixel array's address travels in its header, so the job needs no second
     // pointer.  w = the entries of all lists together, h = 1; read by the kList == 2 instances only.
+    //
+    // Ray list (mm_trace_rays, `list` == kListRays): the launch is w = n_rays, h = 1, one frame, no camera, and
+    // entry e's path starts from record e of the device array `rays`, two float4: (ox, oy, oz, key) and
+    // (dx, dy, dz, -), mm_query_rays' record with the RNG key's bits in word 3.  Every entry is traced.  Read by
+    // the kList == 3 instances only.
     union {
         const float* cams = nullptr;
         const uint2* pixels;
         const uint32_t* lists;
+        const float4* rays;
     };
 };
+constexpr uint32_t kListRays = 3;
 static_assert(sizeof(TileJob) == 224, "the kernel-argument layout the tile instances were measured with");
 constexpr uint32_t kCamStride = 16;
 static_assert(sizeof(mm_camera) <= kCamStride * sizeof(float), "a camera record holds an mm_camera");

@@ -194,27 +194,42 @@ LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mo
     return p;
 }
 
-LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels) {
+namespace {
+
+// One list of n entries in one launch of the plain body's list instances: plan_pixels' and plan_rays' rule.
+// name: the call's; a_list / the_list: how its texts speak of the list.
+LaunchPlan plan_one_list(const std::string& name, const char* a_list, const char* the_list, const PlanOptions& o,
+                         const mm_ext& e, uint64_t n) {
     if (o.pipe == MM_PIPE_WAVEFRONT)
-        return refuse<LaunchPlan>(MM_ERR_UNSUPPORTED, "mm_trace_pixels: MM_PIPE_WAVEFRONT runs the tail rings, which "
-                                                      "a pixel list never does");
+        return refuse<LaunchPlan>(MM_ERR_UNSUPPORTED, name + ": MM_PIPE_WAVEFRONT runs the tail rings, which " +
+                                                          a_list + " never does");
     const bool persist = o.pipe != MM_PIPE_REFERENCE && o.opt_persist == 2;
-    // (n_pixels < 2^63 / 4096 first: the product below cannot wrap)
-    if (n_pixels > 0xFFFFFFFFull || e.spp == 0)
-        return refuse<LaunchPlan>(MM_ERR_INVALID, "mm_trace_pixels: more paths than one launch holds (2^32)");
-    const uint64_t paths = n_pixels * e.spp;
+    // (n < 2^63 / 4096 first: the product below cannot wrap)
+    if (n > 0xFFFFFFFFull || e.spp == 0)
+        return refuse<LaunchPlan>(MM_ERR_INVALID, name + ": more paths than one launch holds (2^32)");
+    const uint64_t paths = n * e.spp;
     const uint64_t queue = ((paths + 63) / 64) * 64;
     if (queue + (1ull << 24) > 0xFFFFFFFFull)
-        return refuse<LaunchPlan>(MM_ERR_INVALID, "mm_trace_pixels: more paths than one launch holds (2^32)");
+        return refuse<LaunchPlan>(MM_ERR_INVALID, name + ": more paths than one launch holds (2^32)");
     LaunchPlan p;
     p.predraw = plan_predraw(o.opt_predraw, o.opt_predraw_pool, e.bounce_limit);
     p.predraw_pool = plan_predraw_pool(o.opt_predraw_pool, e.bounce_limit);
     p.fuse = persist && o.opt_fuse && 64 % e.spp == 0;
     p.rows_per_batch = 1;
     if (!p.fuse && paths > kStagePathsMax)
-        return refuse<LaunchPlan>(MM_ERR_INVALID, "mm_trace_pixels: the list's staged samples exceed 6 GiB (2^29 "
-                                                  "paths); use a shorter list");
+        return refuse<LaunchPlan>(MM_ERR_INVALID, name + ": " + the_list + "'s staged samples exceed 6 GiB (2^29 "
+                                                      "paths); use a shorter list");
     return p;
+}
+
+}  // namespace
+
+LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels) {
+    return plan_one_list("mm_trace_pixels", "a pixel list", "the list", o, e, n_pixels);
+}
+
+LaunchPlan plan_rays(const PlanOptions& o, const mm_ext& e, uint64_t n_rays) {
+    return plan_one_list("mm_trace_rays", "a ray list", "the ray list", o, e, n_rays);
 }
 
 int lists_total(const uint64_t* offsets, uint32_t n_lists, uint64_t& total, std::string& error) {

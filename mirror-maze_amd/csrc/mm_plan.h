@@ -90,6 +90,10 @@ LaunchPlan plan_tile(const SceneFacts& f, const PlanOptions& o, int form, int mo
 // spp in chunks padded to 64, beyond the 32-bit counter (less the 2^24 the waves' last claims may overshoot),
 // or staged samples beyond kStagePathsMax.  rows_per_batch is 1.
 LaunchPlan plan_pixels(const PlanOptions& o, const mm_ext& e, uint64_t n_pixels);
+// A ray-list launch (mm_trace_rays): n_rays entries of e.spp samples in ONE launch, w = n_rays, h = 1, by
+// plan_pixels' rule throughout -- no tail rings (MM_PIPE_WAVEFRONT: MM_ERR_UNSUPPORTED), the same fuse / stage
+// choice, the same queue and staging bounds; the texts carry the call's name.
+LaunchPlan plan_rays(const PlanOptions& o, const mm_ext& e, uint64_t n_rays);
 
 // The pixel lists of several frames in ONE launch (mm_trace_pixel_lists): list f is entries offsets[f] ..
 // offsets[f + 1] - 1 of the concatenated pixel array.  Each list's paths, entries * spp, are padded to whole

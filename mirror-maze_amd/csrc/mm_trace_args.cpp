@@ -90,6 +90,27 @@ ArgCheck check_trace_lists(bool lists, bool var, const mm_uniform* u, const mm_e
     return {};
 }
 
+ArgCheck check_trace_rays(const mm_ext* e, uint32_t ray_flags, const float* rays_dev, uint64_t n_rays,
+                          const void* out_dev, const float* var_dev) {
+    const char* name = "mm_trace_rays";
+    if (n_rays == 0) return {};
+    if (!e || !rays_dev || !out_dev) return bad(name, "null argument");
+    const bool rgba8 = (e->flags & MM_EXT_RGBA8) != 0;
+    const size_t out_bpp = rgba8 ? 4 : 16;
+    if (misaligned(rays_dev, 16) || misaligned(out_dev, out_bpp))
+        return bad(name, "rays not 16-byte or output not " + std::to_string(out_bpp) + "-byte aligned");
+    if (ray_flags & ~MM_RAYS_JITTER) return bad(name, "unknown ray_flags");
+    if (e->spp == 0 || e->spp > 4096) return bad(name, "bad spp");
+    if (e->bounce_limit > 32767 || e->mirror_limit > 32767) return bad(name, "bounce or mirror limit above 32767");
+    if (rgba8 && (e->flags & MM_EXT_ACCUMULATE)) return bad(name, "MM_EXT_RGBA8 results cannot accumulate");
+    if (var_dev) {
+        if (n_rays > 0xFFFFFFFFull)  // (the plan's own refusal, ahead of the byte counts below)
+            return bad(name, "more paths than one launch holds (2^32)");
+        return check_var(name, e, out_dev, n_rays * out_bpp, var_dev, n_rays);
+    }
+    return {};
+}
+
 ArgCheck check_trace_aov(const mm_uniform* u, bool has_cams, uint32_t n_frames, uint32_t mirror_limit, uint32_t x0,
                          uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, const mm_aov* out) {
     const char* name = "mm_trace_aov";

@@ -41,6 +41,14 @@ ArgCheck check_trace_lists(bool lists, bool var, const mm_uniform* u, const mm_e
                            uint32_t n_lists, const uint32_t* pixels_dev, const void* out_dev, const float* var_dev,
                            uint64_t& n_entries);
 
+// mm_trace_rays, in the order include/mm_api.h states: MM_OK with n_rays == 0 (nothing else checked); a null
+// ext, rays_dev or out_dev; a misaligned rays_dev (16 bytes) or out_dev (16, or 4 with MM_EXT_RGBA8); unknown
+// ray_flags; spp, then the limits, out of range; MM_EXT_RGBA8 with MM_EXT_ACCUMULATE; with var_dev, the variance
+// conditions (check_var, under the call's own name; a misaligned var_dev is found there).  The queue and staging
+// bounds are the plan's (mm_plan.h plan_rays), which the call consults next.
+ArgCheck check_trace_rays(const mm_ext* e, uint32_t ray_flags, const float* rays_dev, uint64_t n_rays,
+                          const void* out_dev, const float* var_dev);
+
 // mm_trace_aov.  has_cams: the call came with cameras.
 ArgCheck check_trace_aov(const mm_uniform* u, bool has_cams, uint32_t n_frames, uint32_t mirror_limit, uint32_t x0,
                          uint32_t y0, uint32_t w, uint32_t h, uint32_t y_stride, const mm_aov* out);

@@ -1,7 +1,8 @@
-// mm_trace_calls.hip — the numbered calls of the C ABI (include/mm_api.h): the seven trace calls
-// (mm_trace_tile, _frames, _cameras, _var; mm_trace_pixels, _var; mm_trace_pixel_lists), mm_trace_aov and
-// mm_query_rays.  Every call checks its arguments first (mm_trace_args.h), then plans (mm_plan.h), stages what
-// the launch reads (mm_stage_ring.h) and enqueues its launches as one call of the context's tracker (mm_calls.h).
+// mm_trace_calls.hip — the numbered calls of the C ABI (include/mm_api.h): the eight trace calls
+// (mm_trace_tile, _frames, _cameras, _var; mm_trace_pixels, _var; mm_trace_pixel_lists; mm_trace_rays),
+// mm_trace_aov and mm_query_rays.  Every call checks its arguments first (mm_trace_args.h), then plans
+// (mm_plan.h), stages what the launch reads (mm_stage_ring.h) and enqueues its launches as one call of the
+// context's tracker (mm_calls.h).
 //
 // The steps the trace calls share stand once -- kernel choice, base job, one launch, resolve, close of the call
 // -- under two bodies: the tile calls' (row batches, deferral, cameras) and the list calls'.
@@ -323,15 +324,52 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
 }
 
 // ---- the list calls ----------------------------------------------------------
+// The launch path the list calls share (pixel lists, ray lists), after their checks and their plan -- whose
+// refusals (the queue and staging bounds) need no kernel: the kernel choice, the staged samples, prep(k) -- what
+// the launch reads, staged on the stream ahead of it --, and one numbered call over the base job `all`, a
+// one-row tile n_entries wide: launch(k, all, launches) names the job's source and enqueues the call's trace
+// launches; with staged samples one resolve follows, over all entries (slot entry * spp + sample); var_dev: and
+// their variance.
+template <typename Prep, typename Launch>
+int list_call(mm_ctx* c, const PlanOptions& opts, const LaunchPlan& plan, const mm_uniform& u, const mm_ext& e,
+              uint64_t n_entries, void* out_dev, float* var_dev, mm_stats* stats, const char* what, Prep&& prep,
+              Launch&& launch) {
+    TraceKernel k;
+    k.want_stats = (e.flags & MM_EXT_COUNT_STATS) != 0;
+    if (int rc0 = choose_kernel(c, scene_facts(c), opts, k)) return rc0;
+    const bool fuse = plan.fuse;
+    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e.spp));
+    if (rc) return rc;
+    if ((rc = prep(k))) return rc;
+    if (k.want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
+    if ((rc = begin_timing(c))) return rc;
+    k.sc = dev_scene(c);
+    TileJob all = base_job(c, u, e, plan, out_dev);
+    all.x0 = 0;
+    all.y0 = 0;
+    all.w = (uint32_t)n_entries;
+    all.h = 1;
+    all.y_stride = 1;
+    c->calls.begin_call();
+    uint32_t launches = 0;
+    rc = launch(k, all, launches);
+    if (!rc && !fuse) {
+        TileJob rj = all;
+        if (rj.list == kListRays) rj.list = 0;  // a ray list names no pixels: the tile's resolve, w = n_rays
+        rc = enqueue_resolve(c, rj, out_dev, var_dev);
+        ++launches;
+    }
+    return end_trace_call(c, rc, false, what, launches, k.want_stats, stats);
+}
+
 // The pixel lists of several frames in one launch (lists: mm_trace_pixel_lists), and one list of one frame
 // (mm_trace_pixels / _var: offsets = {0, n_pixels}, no cameras, no keys): the checks, the plan (mm_plan.h
-// plan_pixel_lists; the one-list calls' is plan_pixels, whose texts are theirs), the kernel choice -- after the
-// plan: its refusals (the queue and staging bounds) need none -- and one launch over the concatenation of the
-// lists: kList == 2 with the list table staged ahead of it, kList == 1 for the one list, which needs no
-// table.  With staged samples, one resolve over the concatenation as ONE list (its slots are global
-// entry * spp + sample).  MM_PIPE_REFERENCE: one unchanged k_trace_mega list launch per non-empty list, each
-// into its own slice of the staged samples, and the same resolve.  var_call: the variance call
-// (mm_trace_pixels_var's conditions; as in trace_tile_impl).
+// plan_pixel_lists; the one-list calls' is plan_pixels, whose texts are theirs) and list_call over the
+// concatenation of the lists: kList == 2 with the list table staged ahead of it, kList == 1 for the one list,
+// which needs no table.  With staged samples, one resolve over the concatenation as ONE list.
+// MM_PIPE_REFERENCE: one unchanged k_trace_mega list launch per non-empty list, each into its own slice of the
+// staged samples, and the same resolve.  var_call: the variance call (mm_trace_pixels_var's conditions; as in
+// trace_tile_impl).
 int trace_lists_impl(mm_ctx* c, bool lists, bool var_call, const mm_uniform* u, const mm_camera* cams,
                      const mm_ext* e, const uint32_t* frame_keys, uint32_t n_lists, const uint32_t* pixels_dev,
                      const uint64_t* offsets, void* out_dev, float* var_dev, mm_stats* stats) {
@@ -346,7 +384,6 @@ int trace_lists_impl(mm_ctx* c, bool lists, bool var_call, const mm_uniform* u, 
     if (n_entries == 0) return MM_OK;
     const size_t out_bpp = (e->flags & MM_EXT_RGBA8) ? 4 : 16;
     HIPC(c, hipSetDevice(c->device));
-    const SceneFacts facts = scene_facts(c);
     PlanOptions opts = plan_options(c);
     if (var_call) opts.opt_fuse = false;  // the variance is taken of the staged samples
     ListsPlan lp;
@@ -360,81 +397,9 @@ int trace_lists_impl(mm_ctx* c, bool lists, bool var_call, const mm_uniform* u, 
         one.n_chunks = (one.n_paths + 63u) / 64u;
         lp.lists.assign(1, one);
     }
-    TraceKernel k;
-    k.want_stats = (e->flags & MM_EXT_COUNT_STATS) != 0;
-    if (int rc0 = choose_kernel(c, facts, opts, k)) return rc0;
-    const bool fuse = lp.plan.fuse;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e->spp));
-    if (rc) return rc;
     auto key_of = [&](uint32_t f) { return frame_keys ? frame_keys[f] : e->frame + f; };
     auto cam_of = [&](uint32_t f) -> const mm_camera& { return cams ? cams[f] : u->cam; };
     const uint32_t* table_dev = nullptr;
-    if (k.persist && lists) {
-        // (a multiple of 16 words, so every table starts on a 64-byte line)
-        rc = stage(c, c->lists, ListTable::words(n_lists), [&](uint32_t* t) {
-            const uintptr_t px = reinterpret_cast<uintptr_t>(pixels_dev);
-            t[ListTable::kPixLo] = (uint32_t)px;
-            t[ListTable::kPixHi] = (uint32_t)((uint64_t)px >> 32);
-            t[ListTable::kLists] = n_lists;
-            t[ListTable::kChunks] = lp.n_chunks;
-            t[ListTable::kRecords] = ListTable::records_at(n_lists);
-            for (uint32_t f = 0; f < n_lists; ++f) {
-                const ListSpan& l = lp.lists[f];
-                t[ListTable::kHeader + f] = l.first_chunk;
-                uint32_t* r = t + ListTable::records_at(n_lists) + (size_t)f * ListTable::kRecWords;
-                std::memcpy(r, &cam_of(f), sizeof(mm_camera));
-                r[ListTable::kKey] = key_of(f);
-                r[ListTable::kFirstChunk] = l.first_chunk;
-                r[ListTable::kNumChunks] = l.n_chunks;
-                r[ListTable::kFirstEntry] = l.first_entry;
-                r[ListTable::kPaths] = l.n_paths;
-                r[ListTable::kEntries] = l.n_entries;
-            }
-            t[ListTable::kHeader + n_lists] = lp.n_chunks;
-        }, table_dev);
-        if (rc) return rc;
-    }
-    if (k.want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
-    if ((rc = begin_timing(c))) return rc;
-    k.sc = dev_scene(c);
-    // the concatenation as one list, a one-row tile n_entries wide whose pixels the list names: the resolve's
-    // job, and the base of the launches'
-    TileJob all = base_job(c, *u, *e, lp.plan, out_dev);
-    all.x0 = 0;
-    all.y0 = 0;
-    all.w = (uint32_t)n_entries;
-    all.h = 1;
-    all.y_stride = 1;
-    all.list = 1;
-    all.pixels = reinterpret_cast<const uint2*>(pixels_dev);
-    c->calls.begin_call();
-    uint32_t launches = 0;
-    if (k.persist) {
-        TileJob job = all;
-        if (lists) {
-            job.list = 2;
-            job.lists = table_dev;
-        }
-        rc = enqueue_trace(c, k, job, c->d_samples);
-        if (!rc) ++launches;
-    } else {
-        for (uint32_t f = 0; f < n_lists && !rc; ++f) {
-            const ListSpan& l = lp.lists[f];
-            if (!l.n_entries) continue;
-            TileJob job = all;
-            job.u.cam = cam_of(f);
-            job.e.frame = key_of(f);
-            job.w = l.n_entries;
-            job.pixels = all.pixels + l.first_entry;
-            job.out = reinterpret_cast<char*>(out_dev) + (size_t)l.first_entry * out_bpp;
-            rc = enqueue_trace(c, k, job, c->d_samples + (size_t)l.first_entry * e->spp);
-            if (!rc) ++launches;
-        }
-    }
-    if (!rc && !fuse) {
-        rc = enqueue_resolve(c, all, out_dev, var_call ? var_dev : nullptr);
-        ++launches;
-    }
     char what[160];
     if (lists)
         snprintf(what, sizeof(what), "%s, %u lists, %llu pixels, %u spp", fn, n_lists, (unsigned long long)n_entries,
@@ -442,7 +407,93 @@ int trace_lists_impl(mm_ctx* c, bool lists, bool var_call, const mm_uniform* u, 
     else
         snprintf(what, sizeof(what), "%s, frame %u, %llu pixels, %u spp", var_call ? "mm_trace_pixels_var" : fn,
                  e->frame, (unsigned long long)n_entries, e->spp);
-    return end_trace_call(c, rc, false, what, launches, k.want_stats, stats);
+    return list_call(
+        c, opts, lp.plan, *u, *e, n_entries, out_dev, var_call ? var_dev : nullptr, stats, what,
+        [&](const TraceKernel& k) -> int {
+            if (!k.persist || !lists) return MM_OK;
+            // (a multiple of 16 words, so every table starts on a 64-byte line)
+            return stage(c, c->lists, ListTable::words(n_lists), [&](uint32_t* t) {
+                const uintptr_t px = reinterpret_cast<uintptr_t>(pixels_dev);
+                t[ListTable::kPixLo] = (uint32_t)px;
+                t[ListTable::kPixHi] = (uint32_t)((uint64_t)px >> 32);
+                t[ListTable::kLists] = n_lists;
+                t[ListTable::kChunks] = lp.n_chunks;
+                t[ListTable::kRecords] = ListTable::records_at(n_lists);
+                for (uint32_t f = 0; f < n_lists; ++f) {
+                    const ListSpan& l = lp.lists[f];
+                    t[ListTable::kHeader + f] = l.first_chunk;
+                    uint32_t* r = t + ListTable::records_at(n_lists) + (size_t)f * ListTable::kRecWords;
+                    std::memcpy(r, &cam_of(f), sizeof(mm_camera));
+                    r[ListTable::kKey] = key_of(f);
+                    r[ListTable::kFirstChunk] = l.first_chunk;
+                    r[ListTable::kNumChunks] = l.n_chunks;
+                    r[ListTable::kFirstEntry] = l.first_entry;
+                    r[ListTable::kPaths] = l.n_paths;
+                    r[ListTable::kEntries] = l.n_entries;
+                }
+                t[ListTable::kHeader + n_lists] = lp.n_chunks;
+            }, table_dev);
+        },
+        [&](const TraceKernel& k, TileJob& all, uint32_t& launches) -> int {
+            // the concatenation as one list whose pixels the list names: the resolve's job, and the base of the
+            // launches'
+            all.list = 1;
+            all.pixels = reinterpret_cast<const uint2*>(pixels_dev);
+            int rc = MM_OK;
+            if (k.persist) {
+                TileJob job = all;
+                if (lists) {
+                    job.list = 2;
+                    job.lists = table_dev;
+                }
+                rc = enqueue_trace(c, k, job, c->d_samples);
+                if (!rc) ++launches;
+                return rc;
+            }
+            for (uint32_t f = 0; f < n_lists && !rc; ++f) {
+                const ListSpan& l = lp.lists[f];
+                if (!l.n_entries) continue;
+                TileJob job = all;
+                job.u.cam = cam_of(f);
+                job.e.frame = key_of(f);
+                job.w = l.n_entries;
+                job.pixels = all.pixels + l.first_entry;
+                job.out = reinterpret_cast<char*>(out_dev) + (size_t)l.first_entry * out_bpp;
+                rc = enqueue_trace(c, k, job, c->d_samples + (size_t)l.first_entry * e->spp);
+                if (!rc) ++launches;
+            }
+            return rc;
+        });
+}
+
+// mm_trace_rays: the ray list (kList == 3), one launch in either pipe.  No uni: the job's is zero and unread.
+int trace_rays_impl(mm_ctx* c, const mm_ext* e, uint32_t ray_flags, const float* rays_dev, uint64_t n_rays,
+                    void* out_dev, float* var_dev, mm_stats* stats) {
+    if (!c) return MM_ERR_INVALID;
+    if (int rc0 = report_failure(c, "; this call was not enqueued")) return rc0;
+    if (!c->has_scene) return fail(c, MM_ERR_NO_SCENE, "mm_trace_rays: no scene uploaded");
+    const ArgCheck ck = check_trace_rays(e, ray_flags, rays_dev, n_rays, out_dev, var_dev);
+    if (ck.code != MM_OK) return fail(c, ck.code, ck.error);
+    if (n_rays == 0) return MM_OK;
+    HIPC(c, hipSetDevice(c->device));
+    PlanOptions opts = plan_options(c);
+    if (var_dev) opts.opt_fuse = false;  // the variance is taken of the staged samples
+    const LaunchPlan plan = plan_rays(opts, *e, n_rays);
+    if (plan.code != MM_OK) return fail(c, plan.code, plan.error);
+    char what[160];
+    snprintf(what, sizeof(what), "mm_trace_rays, frame %u, %llu rays, %u spp", e->frame, (unsigned long long)n_rays,
+             e->spp);
+    return list_call(
+        c, opts, plan, mm_uniform{}, *e, n_rays, out_dev, var_dev, stats, what,
+        [](const TraceKernel&) -> int { return MM_OK; },
+        [&](const TraceKernel& k, TileJob& all, uint32_t& launches) -> int {
+            all.list = kListRays;
+            all.rays = reinterpret_cast<const float4*>(rays_dev);
+            all.ray_jitter = (ray_flags & MM_RAYS_JITTER) ? 1u : 0u;
+            const int rc = enqueue_trace(c, k, all, c->d_samples);
+            if (!rc) ++launches;
+            return rc;
+        });
 }
 
 // ---- the query calls ---------------------------------------------------------
@@ -527,6 +578,11 @@ int mm_trace_pixel_lists(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, 
                          const uint64_t* offsets, void* out_dev, float* var_dev, mm_stats* stats) {
     return trace_lists_impl(c, true, var_dev != nullptr, u, cams, e, frame_keys, n_lists, pixels_dev, offsets, out_dev,
                             var_dev, stats);
+}
+
+int mm_trace_rays(mm_ctx* c, const mm_ext* e, uint32_t ray_flags, const float* rays_dev, uint64_t n_rays,
+                  void* out_dev, float* var_dev, mm_stats* stats) {
+    return trace_rays_impl(c, e, ray_flags, rays_dev, n_rays, out_dev, var_dev, stats);
 }
 
 int mm_query_rays(mm_ctx* c, const float* rays_dev, uint64_t n_rays, void* hits_dev) {

@@ -79,6 +79,20 @@ __device__ __forceinline__ bool list_pixel_at(const uint2* __restrict__ pixels, 
     return r.x < job.view_w && r.y < (uint32_t)job.u.view_h;
 }
 
+// Sample smp of entry e (< job.w) of a ray-list launch (mm_trace_rays): its record, two 16-byte loads, into the
+// path's origin, direction and RNG state.  The seed is the tile's function of (key, sample, frame) with the
+// record's word 3 as the key; with job.ray_jitter (launch-uniform) the direction gets the primary ray's jitter,
+// the seed's first two draws, else nothing is drawn before the first bounce.
+__device__ __forceinline__ void ray_start(const TileJob& job, uint32_t e, uint32_t smp, F3& ori, F3& dir,
+                                          uint32_t& seed) {
+    const float4* r = job.rays + 2u * (size_t)e;
+    const float4 a = r[0], b = r[1];
+    seed = seed_tile(__float_as_uint(a.w), smp, job.e.frame);
+    ori = F3{a.x, a.y, a.z};
+    dir = F3{b.x, b.y, b.z};
+    if (job.ray_jitter) dir = jitter(dir, seed);
+}
+
 // The pixel's mean, sum / spp: when spp = 2^k as sum * 2^-k (both are the
 // exact sum x 2^-k rounded once: the same float, without three IEEE divisions).
 __device__ __forceinline__ F3 pixel_mean(F3 acc, uint32_t spp) {

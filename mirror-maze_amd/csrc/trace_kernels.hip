@@ -106,8 +106,9 @@ hipError_t launch_trace_chunks(const DevScene& sc, const mm_uniform& u, const ui
 // everywhere).  (The round-1 one-thread-per-path kernels over the production
 // BVH loop forms measured slower than the wave-persistent kernel and were
 // removed in round 6)
-// kList (mm_trace_pixels): pixel pix is record pix of job.pixels; an entry outside the view runs no path.
-template <bool kStats, bool kList, typename Q>
+// kList 1 (mm_trace_pixels): pixel pix is record pix of job.pixels; an entry outside the view runs no path.
+// kList 3 (mm_trace_rays): path e * spp + s starts from record e of job.rays (mm_wave_util.h ray_start).
+template <bool kStats, int kList, typename Q>
 __device__ __forceinline__ void mega_body(const DevScene& sc, const Q& q, const TileJob& job,
                                           Sample* __restrict__ samples, unsigned long long* stats, uint32_t* err) {
     const uint32_t spp = job.e.spp;
@@ -116,16 +117,22 @@ __device__ __forceinline__ void mega_body(const DevScene& sc, const Q& q, const 
     Counters c;
     bool valid = path < n_paths;
     uint32_t lx = 0, ly = 0;
-    if constexpr (kList) {
+    if constexpr (kList == 1) {
         if (valid) valid = list_pixel(job, path / spp, lx, ly);
     }
     if (valid) {
         const uint32_t pix = path / spp, smp = path - pix * spp;
-        const uint32_t j = pix / job.w, i = pix - j * job.w;
-        const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
-        uint32_t seed = seed_tile(py * job.view_w + px, smp, job.e.frame);
-        const F3 d = jitter(primary_dir(job.u, px, py), seed);
-        const F3 ori = F3{job.u.cam.center[0], job.u.cam.center[1], job.u.cam.center[2]};
+        uint32_t seed;
+        F3 d, ori;
+        if constexpr (kList == kListRays) {
+            ray_start(job, pix, smp, ori, d, seed);
+        } else {
+            const uint32_t j = pix / job.w, i = pix - j * job.w;
+            const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
+            seed = seed_tile(py * job.view_w + px, smp, job.e.frame);
+            d = jitter(primary_dir(job.u, px, py), seed);
+            ori = F3{job.u.cam.center[0], job.u.cam.center[1], job.u.cam.center[2]};
+        }
         ScratchStack stack;
         bool overflow = false;
         const F3 s = trace_path<kStats>(sc, q, ori, d, seed, (int)job.e.bounce_limit, (int)job.e.mirror_limit, stack,
@@ -136,7 +143,7 @@ __device__ __forceinline__ void mega_body(const DevScene& sc, const Q& q, const 
     if (kStats) flush_stats(stats, c, valid ? 1u : 0u);
 }
 
-template <bool kStats, bool kList = false>
+template <bool kStats, int kList = 0>
 __global__ __launch_bounds__(1024) void k_trace_mega(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                      unsigned long long* stats, uint32_t* err) {
     mega_body<kStats, kList>(sc, RefQuery<kStats>{sc}, job, samples, stats, err);
@@ -538,6 +545,12 @@ __device__ __forceinline__ const uint2* list_pixels(const TileJob& job) {
 // valid below the list's paths, and its entry is the list's first global entry + path / spp -- out, the staged
 // samples (slot entry * spp + sample) and store_unlisted are indexed by that global entry.  The camera and the
 // RNG frame are the list's.  With 64 % spp == 0 a pixel's samples never straddle a chunk, as in a single list.
+//
+// Ray-list launches (kList == kListRays, mm_trace_rays; w = n_rays, h = 1, one frame): queue slot `path` starts
+// from record path / spp of job.rays (mm_wave_util.h ray_start) -- two 16-byte loads per lane, spp consecutive
+// lanes the same record, a chunk's 64 lanes at most 64 consecutive records --, consumed into p.ori, p.dir and
+// p.sb before the pre-pass.  Every entry is valid (nothing is unlisted), and out and the staged samples are the
+// tile's: entry path / spp, slot path.
 template <bool kStats, bool kCams, int kList, typename Q>
 __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q& q, const TileJob& job,
                                                      Sample* __restrict__ samples, unsigned long long* stats,
@@ -592,8 +605,11 @@ __device__ __forceinline__ uint32_t wavepersist_body(const DevScene& sc, const Q
             const uint32_t j = pix / job.w, i = pix - j * job.w;
             const uint32_t px = kList ? lx : job.x0 + i, py = kList ? ly : job.y0 + j * job.y_stride;
             PathState p;
-            p.sb = seed_tile(py * job.view_w + px, smp, kList == 2 ? lc.key : job.e.frame + fr);
-            if constexpr (kList == 2) {  // the list's camera, per chunk as a camera sequence's
+            if constexpr (kList != kListRays)
+                p.sb = seed_tile(py * job.view_w + px, smp, kList == 2 ? lc.key : job.e.frame + fr);
+            if constexpr (kList == kListRays) {  // the caller's ray: no pixel, no camera
+                ray_start(job, pix, smp, p.ori, p.dir, p.sb);
+            } else if constexpr (kList == 2) {  // the list's camera, per chunk as a camera sequence's
                 const mm_uniform cu = list_uniform(job, lc.f);
                 p.dir = jitter(primary_dir(cu, px, py), p.sb);
                 p.ori = F3{cu.cam.center[0], cu.cam.center[1], cu.cam.center[2]};
@@ -1005,6 +1021,8 @@ constexpr uint32_t kWpThreads = MM_WP_THREADS;
 // kList: a pixel-list launch (job.pixels, mm_trace_pixels), built for kRing = 0 and kCams = false only; the
 // tile instances' code is the same with and without the feature (gate: profiles/pixels/kernel_resources.txt).
 // kList == 2: the pixel lists of several frames (job.lists, mm_trace_pixel_lists), under kList == 1's conditions.
+// kList == 3 (kListRays): a ray list (job.rays, mm_trace_rays), under kList == 1's conditions; the existing
+// instances' code is the same with and without it (gate: profiles/rays/kernel_resources.txt).
 template <bool kStats, int kLds, int kForm, int kRing, bool kCams = false, int kList = 0>
 __global__ __launch_bounds__(MM_WP_THREADS, MM_WP_WAVES) void k_trace_wavepersist(DevScene sc, TileJob job, Sample* __restrict__ samples,
                                                                unsigned long long* stats, uint32_t* err,
@@ -1066,10 +1084,13 @@ static hipError_t launch_wavepersist_t(const DevScene& sc, const TileJob& job, S
     const size_t lds = lds_static_grid(kLds) ? 0 : wavepersist_lds_bytes(sc, kLds);
     auto kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, kRing>
                             : k_trace_wavepersist<false, kLds, kForm, kRing>;
-    if (job.list) {  // a pixel list: the plain body's instances, one frame
+    if (job.list) {  // a pixel or ray list: the plain body's instances, one frame
         if constexpr (kRing == 0) {
             if (job.n_frames != 1) return hipErrorInvalidValue;
-            if (job.list == 2)
+            if (job.list == kListRays)
+                kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, 3>
+                                   : k_trace_wavepersist<false, kLds, kForm, 0, false, 3>;
+            else if (job.list == 2)
                 kern = count_stats ? k_trace_wavepersist<true, kLds, kForm, 0, false, 2>
                                    : k_trace_wavepersist<false, kLds, kForm, 0, false, 2>;
             else
@@ -1131,10 +1152,14 @@ hipError_t launch_trace_mega(const DevScene& sc, const TileJob& job, Sample* sam
     if (!o.reference) return hipErrorInvalidValue;  // one thread per path: MM_PIPE_REFERENCE only
     const uint32_t n = job.w * job.h * job.e.spp;
     const dim3 grid((n + o.block - 1) / o.block);
-    if (job.list && count_stats)
-        hipLaunchKernelGGL((k_trace_mega<true, true>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+    if (job.list == kListRays && count_stats)
+        hipLaunchKernelGGL((k_trace_mega<true, 3>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+    else if (job.list == kListRays)
+        hipLaunchKernelGGL((k_trace_mega<false, 3>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+    else if (job.list && count_stats)
+        hipLaunchKernelGGL((k_trace_mega<true, 1>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
     else if (job.list)
-        hipLaunchKernelGGL((k_trace_mega<false, true>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
+        hipLaunchKernelGGL((k_trace_mega<false, 1>), grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
     else if (count_stats)
         hipLaunchKernelGGL(k_trace_mega<true>, grid, dim3(o.block), 0, s, sc, job, samples, stats_dev, err);
     else

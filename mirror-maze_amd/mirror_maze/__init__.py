@@ -18,6 +18,8 @@ from ._lib import MM_DENOISE_MAX_PASSES, MM_DN_RGBA8, mm_denoise_params  # noqa:
 from ._lib import MM_DNV_RGBA8, mm_denoise_var_params  # noqa: F401
 from ._lib import mm_temporal_params, mm_temporal_prev, mm_temporal_prev_var  # noqa: F401
 from ._lib import mm_upsample_params  # noqa: F401
+from ._lib import MM_RAYS_JITTER  # noqa: F401
+from .rays import equirect_rays, ortho_rays, pack_rays  # noqa: F401
 from .renderer import Renderer, make_ext  # noqa: F401
 from .sampling import (merge_samples, select_holes, select_holes_frames, select_noisy, select_noisy_frames,  # noqa: F401
                        select_short_history)
@@ -25,4 +27,4 @@ from .scene import (ChunkScheduler, Player, Scene, calculate_quaternion, check_c
                     walk_cameras)
 
 __all__ = ["Renderer", "Scene", "ChunkScheduler", "Player", "check_collision", "default_uniform", "calculate_quaternion", "make_ext",
-           "walk_cameras", "select_short_history", "select_noisy", "select_noisy_frames", "select_holes", "select_holes_frames", "merge_samples", "mm_aov", "mm_upsample_params", "mm_denoise_params", "mm_denoise_var_params", "mm_temporal_params", "mm_temporal_prev", "mm_temporal_prev_var", "mm_camera", "mm_ext", "mm_stats", "mm_uniform", "MMError", "lib"]
+           "walk_cameras", "select_short_history", "select_noisy", "select_noisy_frames", "select_holes", "select_holes_frames", "merge_samples", "pack_rays", "equirect_rays", "ortho_rays", "mm_aov", "mm_upsample_params", "mm_denoise_params", "mm_denoise_var_params", "mm_temporal_params", "mm_temporal_prev", "mm_temporal_prev_var", "mm_camera", "mm_ext", "mm_stats", "mm_uniform", "MMError", "lib"]

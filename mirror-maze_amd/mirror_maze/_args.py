@@ -1,5 +1,5 @@
 """What Renderer's methods do to their arguments before a C call, where it needs no context: the one tensor
-check, camera and pixel-list conversion, the offsets and frame keys of trace_pixel_lists, and the two ext
+check, camera, pixel-list and ray-list conversion, the offsets and frame keys of trace_pixel_lists, and the two ext
 builders.  Each caller keeps its own refusal text."""
 from __future__ import annotations
 
@@ -82,6 +82,15 @@ def pixel_list(pixels, device):
     if not tensor_ok(pixels, torch.int32, ((None, 2),)):
         raise ValueError("pixels must be a contiguous int32 / uint32 (n, 2) CUDA tensor or an (n, 2) array")
     return pixels
+
+
+def ray_list(rays):
+    """trace_rays' records: `rays` itself, a contiguous (n, 8) float32 CUDA tensor."""
+    import torch
+
+    if not tensor_ok(rays, torch.float32, ((None, 8),)):
+        raise ValueError("rays must be a contiguous float32 (n, 8) CUDA tensor")
+    return rays
 
 
 def list_offsets(offsets, n) -> np.ndarray:

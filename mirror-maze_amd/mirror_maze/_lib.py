@@ -32,6 +32,7 @@ class MMError(RuntimeError):
 MM_OK, MM_ERR_INVALID, MM_ERR_HIP, MM_ERR_NOMEM = 0, -1, -2, -3
 MM_ERR_NO_SCENE, MM_ERR_STACK, MM_ERR_UNSUPPORTED = -4, -5, -6
 MM_EXT_COUNT_STATS, MM_EXT_ACCUMULATE, MM_EXT_RGBA8 = 0x1, 0x2, 0x4
+MM_RAYS_JITTER = 0x1  # mm_trace_rays' ray_flags
 MM_PIPE_AUTO, MM_PIPE_MEGAKERNEL, MM_PIPE_WAVEFRONT, MM_PIPE_REFERENCE = 0, 1, 2, 3
 MM_OPT_LDS_NODES, MM_OPT_BLOCK, MM_OPT_PERSIST, MM_OPT_TRAVERSAL, MM_OPT_LDS_RECTS = 1, 2, 3, 7, 8
 MM_OPT_LDS_SPLIT, MM_OPT_FUSE_RESOLVE, MM_OPT_RESERVE_CUS, MM_OPT_DICT_NODES, MM_OPT_DEFER = 9, 12, 19, 20, 21
@@ -172,6 +173,7 @@ EXPORTS = {
                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, C.POINTER(mm_stats)]),
     "mm_trace_pixels_var": (C.c_int, [P, C.POINTER(mm_uniform), C.POINTER(mm_ext), P, C.c_uint64, P, P,
                                       C.POINTER(mm_stats)]),
+    "mm_trace_rays": (C.c_int, [P, C.POINTER(mm_ext), C.c_uint32, P, C.c_uint64, P, P, C.POINTER(mm_stats)]),
     "mm_trace_pixel_lists": (C.c_int, [P, C.POINTER(mm_uniform), P, C.POINTER(mm_ext), P, C.c_uint32, P, P, P, P,
                                        C.POINTER(mm_stats)]),
     "mm_upsample_frames": (C.c_int, [P, P, C.POINTER(mm_aov), P, C.POINTER(mm_upsample_params), C.c_uint32, C.c_uint32,

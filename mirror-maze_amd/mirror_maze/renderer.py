@@ -541,6 +541,35 @@ class Renderer:
         return self._trace(lambda e, st: lib().mm_trace_pixels(self._ctx, C.byref(uniform), e, _ptr(pixels, n), n,
                                                                _ptr(out, n), st), ext, stats, r8, out)
 
+    def trace_rays(self, ext: _lib.mm_ext, rays, jitter: bool = False, out=None, var=None, stats: bool = False,
+                   rgba8: bool = False):
+        """Shaded radiance along n caller-supplied rays (mm_trace_rays).  `rays`:
+        an (n, 8) float32 CUDA tensor, ray i = (origin xyz, RNG key bits,
+        direction xyz, -), as rays.pack_rays builds it.  Entry e of the (n, 4)
+        float32 result (`out` if given; uint8 RGBA8 with rgba8 / a uint8 `out`,
+        as trace_tile) is the mean of ext.spp paths from the ray; jitter: the
+        primary ray's jitter on the direction (MM_RAYS_JITTER).  `var`: True,
+        or an (n,) float32 CUDA tensor, for each entry's sample variance as
+        trace_pixels_var defines it.  Returns (out, mm_stats or None), or
+        (out, var, mm_stats or None) with `var`."""
+        import torch
+
+        rays = _args.ray_list(rays)
+        n = rays.shape[0]
+        out, r8 = self._out(out, (n, 4), rgba8, rays.device)
+        if var is True:
+            var = torch.zeros((n,), dtype=torch.float32, device=rays.device)
+        elif var is False:
+            var = None
+        if var is not None and not tensor_ok(var, torch.float32, ((n,),)):
+            raise ValueError(f"var must be a contiguous float32 CUDA tensor of {n} elements")
+        self._follow(out.device)
+        flags = _lib.MM_RAYS_JITTER if jitter else 0
+        outs = (out,) if var is None else (out, var)
+        return self._trace(lambda e, st: lib().mm_trace_rays(self._ctx, e, flags, _ptr(rays, n), n, _ptr(out, n),
+                                                             None if var is None else _ptr(var, n), st),
+                           ext, stats, r8, *outs)
+
     def blend_pixels(self, image, pixels, extra, m: float, x0: int = 0, y0: int = 0):
         """Blend extra samples into an accumulated frame, in place
         (mm_blend_pixels).  `image`: the (h, w, 4) float32 CUDA tensor of the

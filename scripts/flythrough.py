@@ -16,6 +16,7 @@ launch per batch), written as PNGs.
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate --top-up 2:24   # + extra samples where the history is short
     python scripts/flythrough.py --maze 32 --frames 40 --accumulate-var --denoise-var   # + frame_NNNN_accv.png, and the variance-guided filter on it
     python scripts/flythrough.py --maze 32 --frames 40 --upsample 2 --denoise          # trace every 2nd pixel, rebuild from the AOVs: frame_NNNN_up.png
+    python scripts/flythrough.py --maze 32 --frames 40 --panorama 2048 --map 1024       # + frame_NNNN_pano.png per frame, one map.png
 
 --aov DIR also writes, per frame, DIR/frame_NNNN/normal.png (the outward normal of
 what the pixel sees through the mirrors, as 0.5 n + 0.5), depth.npy (float32
@@ -93,6 +94,17 @@ either of the last two the lattice is traced with its variance -- in one launch
 where a multi-frame variance launch runs, else frame by frame.
 Not with --accumulate, --refine or --top-up.
 
+--panorama W also writes frame_NNNN_pano.png (W x W/2) beside each frame: the
+360-degree equirectangular view from the frame's camera, its centre looking
+where the frame looks, through Renderer.trace_rays (mm_trace_rays) over
+mirror_maze.equirect_rays, with RNG frame f and --spp / --bounces / --mirrors.
+
+--map W writes one map.png (W x W): the maze from above, orthographic
+(mirror_maze.ortho_rays), the walk's camera positions marked in red.  The rays
+point from the ceiling to the floor and start 5 % of the room's height BELOW
+the ceiling rect: started above it they would show the ceiling and nothing
+else, and the corridors are what the map is for.
+
 The camera path is printed one frame per line (floats as %.9g, which a float32
 survives): frame, center, quat -- the camera after that frame's step.
 """
@@ -115,6 +127,32 @@ def key_script(n_frames: int, turn_every: int, turn_dx: float):
 
     return [([Player.KEY_W], [turn_dx] if turn_every and f % turn_every == turn_every - 1 else [])
             for f in range(n_frames)]
+
+
+def top_down_map(r, scene, cams, width, ext):
+    """The (width, width, 4) uint8 map of --map: the scene's footprint in x and z seen from above through
+    Renderer.trace_rays, the cameras' positions in red.  +y is down (a camera's image-down axis): of the
+    horizontal rects the ceiling is the one with the least y, the floor the one with the greatest (the walls reach
+    above the ceiling), and the rays start 5 % of the room's height below the ceiling."""
+    import numpy as np
+
+    from mirror_maze import ortho_rays
+
+    rects = scene.rects
+    corners = np.concatenate([rects[:, 0:3], rects[:, 0:3] + rects[:, 3:6], rects[:, 0:3] + rects[:, 6:9],
+                              rects[:, 0:3] + rects[:, 3:6] + rects[:, 6:9]])
+    lo, hi = corners.min(axis=0), corners.max(axis=0)
+    side = float(max(hi[0] - lo[0], hi[2] - lo[2]))
+    level = rects[np.cross(rects[:, 3:6], rects[:, 6:9])[:, 1] != 0.0, 1]  # the horizontal rects' heights
+    ceiling, floor = (float(level.min()), float(level.max())) if len(level) else (float(lo[1]), float(hi[1]))
+    y = ceiling + 0.05 * (floor - ceiling)
+    rays = ortho_rays([lo[0], y, lo[2]], [side, 0.0, 0.0], [0.0, 0.0, side], [0.0, 1.0, 0.0], width, width)
+    img, _ = r.trace_rays(ext, rays, rgba8=True)
+    img = img.view(width, width, 4).cpu().numpy().copy()
+    for c in cams:
+        i, j = int((c[0] - lo[0]) / side * width), int((c[2] - lo[2]) / side * width)
+        img[max(0, j - 1):j + 2, max(0, i - 1):i + 2] = (255, 0, 0, 255)
+    return img
 
 
 def main(argv=None) -> int:
@@ -155,10 +193,19 @@ def main(argv=None) -> int:
                     help="trace the lattice of every S-th pixel (S = 2, 4 or 8) and rebuild the frames from the feature "
                          "buffers (Renderer.trace_upsampled): writes frame_NNNN_up.png; composes with --denoise, "
                          "--denoise-var and --accumulate-var")
+    ap.add_argument("--panorama", metavar="W", type=int, default=0,
+                    help="also write frame_NNNN_pano.png: a W x W/2 equirectangular panorama from each frame's camera "
+                         "(Renderer.trace_rays)")
+    ap.add_argument("--map", metavar="W", type=int, default=0,
+                    help="also write map.png: a W x W orthographic view of the maze from above with the walk marked; "
+                         "the rays start 5 %% of the room's height below the ceiling (from above it the map would "
+                         "show the ceiling rect) and point at the floor")
     ap.add_argument("--no-render", action="store_true", help="print the camera path only (needs no GPU)")
     a = ap.parse_args(argv)
     if a.frames < 1 or a.batch < 1:
         ap.error("--frames and --batch must be positive")
+    if a.panorama < 0 or a.panorama % 2 or a.map < 0:
+        ap.error("--panorama takes an even width, --map a width")
     if a.accumulate and a.accumulate_var:
         ap.error("--accumulate-var is a mode of its own: not with --accumulate")
     if a.denoise_var and a.accumulate:
@@ -233,9 +280,21 @@ def main(argv=None) -> int:
     prev = None  # --accumulate: the last accumulated frame, its feature buffers and its camera (-var: and its variance)
     with Renderer(0) as r:
         r.upload_scene(scene)
+        if a.map:
+            write_png(out_dir / "map.png", top_down_map(r, scene, cams, a.map, make_ext(a.spp, a.bounces, a.mirrors)))
+            print(f"# map: {out_dir}/map.png", flush=True)
         for f0 in range(0, a.frames, a.batch):
             batch = cams[f0:f0 + a.batch]
             e = make_ext(a.spp, a.bounces, a.mirrors, frame=f0)
+            if a.panorama:
+                from mirror_maze import equirect_rays
+
+                for k in range(len(batch)):
+                    rays = equirect_rays(batch[k][0:3], batch[k][4:8], a.panorama, a.panorama // 2)
+                    pano, _ = r.trace_rays(make_ext(a.spp, a.bounces, a.mirrors, frame=f0 + k), rays, rgba8=True)
+                    write_png(out_dir / f"frame_{f0 + k:04d}_pano.png",
+                              pano.view(a.panorama // 2, a.panorama, 4).cpu().numpy())
+                print(f"# frames {f0}..{f0 + len(batch) - 1}: panoramas, {out_dir}/frame_{f0:04d}_pano.png ...", flush=True)
             # one launch for the batch where a multi-frame variance call runs: at most the 2^29 paths a launch
             # stages, and the tail deferral such a launch needs (from MM_OPT_DEFER_MIN's 2^24 paths on, where the
             # plan has it; the call refuses the launch otherwise, before anything is enqueued)
