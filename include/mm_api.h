@@ -20,6 +20,17 @@
  * bound to one GPU and is not thread-safe (the reference drives Metal from one
  * main thread too, src/main.rs:591).  All work is enqueued on the context's
  * stream; mm_sync waits for it (the reference never waits, src/main.rs:894).
+ *
+ * One context, several streams: the trace, query and parity-mode calls of a
+ * context share device state -- one work counter, the staged samples, the tail
+ * rings, the statistics and error words, the framebuffer -- so they run one
+ * after the other, in the order they were made.  On one stream that is stream
+ * order.  When the stream was changed in between (mm_set_stream), the new
+ * stream first waits, on the device, for the end of the last such call made
+ * on the other stream; the host never waits for this, and nothing is added
+ * while the stream stays the same.  The caller's buffers are the caller's: a
+ * call that reads what a call on another stream wrote is ordered by the
+ * caller, as between any two streams.
  */
 #ifndef MM_API_H
 #define MM_API_H
@@ -43,7 +54,11 @@ const char* mm_last_error(const mm_ctx* ctx);
 
 /* Enqueue on a caller stream (hipStream_t passed as void*), e.g. torch's
  * current stream.  NULL is HIP's default (null) stream, as in HIP itself;
- * MM_OWN_STREAM restores the context's own non-blocking stream. */
+ * MM_OWN_STREAM restores the context's own non-blocking stream.  Only stores
+ * the handle: the next trace, query or parity-mode call on the new stream
+ * waits there for the context's last such call on the old one (see the head
+ * of this file), so the context may be moved between streams without a sync
+ * in between.  The streams must outlive the work enqueued on them. */
 #define MM_OWN_STREAM ((void*)(intptr_t)-1)
 int  mm_set_stream(mm_ctx* ctx, void* hip_stream);
 /* The stream work is enqueued on (after mm_set_stream; initially the
@@ -56,7 +71,18 @@ int  mm_get_stream(const mm_ctx* ctx, void** hip_stream);
  *   idx        buffer 3  indices      n_rects x u32
  *   is_mirror  buffer 5  materials    n_rects x 1 B (bool)
  *   emission   buffer 6  emissions    n_rects x float4
- * Copies the data; validates the tree (indices in range, stack depth <= 50). */
+ * Copies the data; validates the tree (indices in range, stack depth <= 50).
+ * On a context that already holds a scene:
+ *   - a successful upload replaces it after all work the context has queued,
+ *     on any stream, has finished (the call waits for the device), so calls
+ *     made before the upload see the old scene and calls after it the new;
+ *   - a refusal of the arguments -- MM_ERR_INVALID, MM_ERR_UNSUPPORTED, and
+ *     MM_ERR_STACK for a tree too deep -- leaves the previous scene in place
+ *     and usable;
+ *   - a failure after that point (MM_ERR_HIP: an allocation or a copy) leaves
+ *     the context without a scene (MM_ERR_NO_SCENE until the next upload).
+ * The MM_OPT_GRID_* options are read here: changing one acts at the next
+ * upload. */
 int  mm_upload_scene(mm_ctx* ctx,
                      const mm_rect* rects, uint32_t n_rects,
                      const mm_node* nodes, uint32_t n_nodes,

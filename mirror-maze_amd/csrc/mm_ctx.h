@@ -90,6 +90,15 @@ struct mm_ctx {
     unsigned long long* d_aux = nullptr;
     uint32_t* d_work = nullptr;  // the wave-persistent kernel's self-cleaning queue heads + waves-done word (4 KB)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // The last call that used the state a context's launches share -- d_work, d_aux, d_samples, d_tail, the
+    // status slots, the parity-mode buffers: its work is done at `shared_done`, recorded on `shared_stream`.  A
+    // later such call on another stream waits for that event first (mm_runtime.hip order_shared), as the denoise
+    // calls do for their scratch (dn_done).  The event is the `ev1` end_timing records after a call's last
+    // launch anyway, so a trace call pays nothing for it; mm_present, which is not timed, records
+    // `present_done`.
+    hipEvent_t shared_done = nullptr;
+    hipStream_t shared_stream = nullptr;
+    hipEvent_t present_done = nullptr;
     float last_ms = 0.0f;
     uint32_t last_launches = 0;
     int pipe = MM_PIPE_AUTO;
@@ -161,9 +170,21 @@ int ensure(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
     return MM_OK;
 }
 
+// ensure for scratch that queued launches may still read, on any stream used so far: grown (never shrunk) after
+// everything the device has queued is done.  The wait costs something only when growing.
+template <typename T>
+int ensure_idle(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
+    if (n <= cap && ptr) return MM_OK;
+    HIPC(c, hipDeviceSynchronize());
+    return ensure(c, ptr, cap, n);
+}
+
 // The runtime's helpers the trace and query calls use too (mm_runtime.hip).
 DevScene dev_scene(const mm_ctx* c);
-// The events around a call's launches (mm_last_timing).
+// Before a call's first use of the state the context's launches share: if the last such call was enqueued on
+// another stream, the context's stream waits for its end (an event wait on the device; the host never waits).
+int order_shared(mm_ctx* c);
+// The events around a call's launches (mm_last_timing).  end_timing's event is also what order_shared waits for.
 int begin_timing(mm_ctx* c);
 int end_timing(mm_ctx* c, uint32_t launches);
 // Reads the statistics (st, if not null) and the sticky error flag back, after a sync of the stream.

@@ -18,15 +18,6 @@ using namespace mm;
 
 namespace {
 
-// A denoise call's scratch of at least `n` elements: grown (never shrunk) after everything the device has queued
-// is done -- an earlier call's passes may still read the old one, on any stream used so far.
-template <typename T>
-int dn_scratch(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
-    if (n <= cap && ptr) return MM_OK;
-    HIPC(c, hipDeviceSynchronize());
-    return ensure(c, ptr, cap, n);
-}
-
 // What a denoise call needs before its passes: the intermediate images a frame's passes alternate between (one
 // frame each; `var`: and the variance images beside them), the call's packed key records, filled here, and its
 // place after the last call's kernels.  The scratch, its event and its stream bookkeeping are one for both
@@ -34,11 +25,11 @@ int dn_scratch(mm_ctx* c, T*& ptr, size_t& cap, size_t n) {
 int dn_begin(mm_ctx* c, bool var, const mm_aov* guides, uint32_t n_passes, uint64_t n_pix, uint64_t n_all) {
     if (n_passes > 1) {
         const size_t sides = n_passes > 2 ? 2 : 1;
-        if (int rc = dn_scratch(c, c->d_dn_img, c->dn_img_cap, sides * (size_t)n_pix)) return rc;
+        if (int rc = ensure_idle(c, c->d_dn_img, c->dn_img_cap, sides * (size_t)n_pix)) return rc;
         if (var)
-            if (int rc = dn_scratch(c, c->d_dn_var, c->dn_var_cap, sides * (size_t)n_pix)) return rc;
+            if (int rc = ensure_idle(c, c->d_dn_var, c->dn_var_cap, sides * (size_t)n_pix)) return rc;
     }
-    if (int rc = dn_scratch(c, c->d_dn_keys, c->dn_keys_cap, (size_t)n_all)) return rc;
+    if (int rc = ensure_idle(c, c->d_dn_keys, c->dn_keys_cap, (size_t)n_all)) return rc;
     if (!c->dn_done) HIPC(c, hipEventCreateWithFlags(&c->dn_done, hipEventDisableTiming));
     if (c->dn_pending && c->dn_stream != c->stream) HIPC(c, hipStreamWaitEvent(c->stream, c->dn_done, 0));
     HIPC(c, launch_denoise_keys(reinterpret_cast<const float4*>(guides->albedo), guides->id, c->d_dn_keys,

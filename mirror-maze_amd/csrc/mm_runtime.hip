@@ -51,12 +51,23 @@ DevScene dev_scene(const mm_ctx* c) {
     return s;
 }
 
+int order_shared(mm_ctx* c) {
+    if (c->shared_done && c->shared_stream != c->stream) HIPC(c, hipStreamWaitEvent(c->stream, c->shared_done, 0));
+    return MM_OK;
+}
+// `done` was just recorded on the context's stream, after the last work of a call that order_shared guards.
+static void shared_until(mm_ctx* c, hipEvent_t done) {
+    c->shared_done = done;
+    c->shared_stream = c->stream;
+}
+
 int begin_timing(mm_ctx* c) {
     HIPC(c, hipEventRecord(c->ev0, c->stream));
     return MM_OK;
 }
 int end_timing(mm_ctx* c, uint32_t launches) {
     HIPC(c, hipEventRecord(c->ev1, c->stream));
+    shared_until(c, c->ev1);
     c->last_launches = launches;
     c->last_ms = -1.0f;  // resolved lazily in mm_last_timing
     return MM_OK;
@@ -197,6 +208,7 @@ void mm_destroy(mm_ctx* c) {
     (void)hipFree(c->d_dn_img); (void)hipFree(c->d_dn_keys); (void)hipFree(c->d_dn_var);
     if (c->dn_done) (void)hipEventDestroy(c->dn_done);
     if (c->gather_done) (void)hipEventDestroy(c->gather_done);
+    if (c->present_done) (void)hipEventDestroy(c->present_done);
     if (c->h_status) (void)hipHostFree(c->h_status);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -399,6 +411,8 @@ int mm_upload_scene(mm_ctx* c, const mm_rect* rects, uint32_t n_rects, const mm_
         for (int a = 0; a < 3; ++a)
             fast = fast && coord_ok(rects[k].o[a]) && extent_ok(rects[k].v[a]) && extent_ok(rects[k].u[a]);
     HIPC(c, hipSetDevice(c->device));
+    // the old scene goes once everything the context has queued, on any stream used so far, is done with it
+    if (c->has_scene) HIPC(c, hipDeviceSynchronize());
     free_scene(c);
     std::vector<float4> shade(2 * (size_t)n_rects);
     for (uint32_t k = 0; k < n_rects; ++k) {
@@ -481,6 +495,7 @@ int mm_trace_chunks(mm_ctx* c, const mm_uniform* u, const uint32_t* chunks, uint
     if (max_pbi >= n_chunks) return fail(c, MM_ERR_INVALID, "mm_trace_chunks: chunk list shorter than the grid");
     const uint32_t W = (uint32_t)u->view_w, H = (uint32_t)u->view_h;
     HIPC(c, hipSetDevice(c->device));
+    if (int rc = order_shared(c)) return rc;
     if (W != c->fb_w || H != c->fb_h) {
         (void)hipFree(c->d_fb); (void)hipFree(c->d_fb8); (void)hipFree(c->d_fb8_alt);
         c->d_fb = nullptr; c->d_fb8 = nullptr; c->d_fb8_alt = nullptr;
@@ -509,8 +524,12 @@ int mm_present(mm_ctx* c) {
     if (!c) return MM_ERR_INVALID;
     if (!c->d_fb8) return fail(c, MM_ERR_INVALID, "mm_present: nothing rendered yet");
     HIPC(c, hipSetDevice(c->device));
+    if (int rc = order_shared(c)) return rc;
+    if (!c->present_done) HIPC(c, hipEventCreateWithFlags(&c->present_done, hipEventDisableTiming));
     HIPC(c, launch_present_blur(c->d_fb8, c->d_fb8_alt, c->fb_w, c->fb_h, c->stream));
     std::swap(c->d_fb8, c->d_fb8_alt);
+    HIPC(c, hipEventRecord(c->present_done, c->stream));
+    shared_until(c, c->present_done);
     return MM_OK;
 }
 
@@ -522,7 +541,8 @@ int mm_read_packets(mm_ctx* c, float* packets, uint32_t n_chunks) {
         return fail(c, MM_ERR_INVALID, "mm_read_packets: more chunks than the last dispatch used");
     if (n_chunks == 0) return MM_OK;
     HIPC(c, hipSetDevice(c->device));
-    int rc = ensure(c, c->d_packets, c->packets_cap, 16 * (size_t)n_chunks);
+    int rc = order_shared(c);
+    if (!rc) rc = ensure(c, c->d_packets, c->packets_cap, 16 * (size_t)n_chunks);
     if (rc) return rc;
     HIPC(c, launch_chunk_packets(c->d_fb, c->d_chunks, n_chunks, c->fb_w, c->fb_h, c->d_packets, c->stream));
     HIPC(c, hipMemcpyAsync(packets, c->d_packets, 16 * (size_t)n_chunks * sizeof(float4), hipMemcpyDeviceToHost,
@@ -548,6 +568,7 @@ int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
     if (!c->d_fb) return fail(c, MM_ERR_INVALID, "mm_read_framebuffer: nothing rendered yet");
     const size_t n = (size_t)c->fb_w * c->fb_h;
     HIPC(c, hipSetDevice(c->device));
+    if (int rc = order_shared(c)) return rc;
     if (rgba) HIPC(c, hipMemcpyAsync(rgba, c->d_fb, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     if (rgba8) HIPC(c, hipMemcpyAsync(rgba8, c->d_fb8, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -557,6 +578,7 @@ int mm_read_framebuffer(mm_ctx* c, float* rgba, uint8_t* rgba8) {
 int mm_sync(mm_ctx* c) {
     if (!c) return MM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
+    if (int rc = order_shared(c)) return rc;  // (the error word is read on the stream: after its last writer)
     HIPC(c, hipStreamSynchronize(c->stream));
     if (int rc = read_aux(c, nullptr)) return rc;
     return report_failure(c, "");

@@ -51,6 +51,7 @@ int tail_queue(mm_ctx* c, TailQueue& q) {
     HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     const uint32_t cap = 2u * (uint32_t)cus * kTailRing;
     if (c->tail_cap < cap || !c->d_tail) {
+        if (c->d_tail) HIPC(c, hipDeviceSynchronize());  // (a queued launch may still use the old rings: ensure_idle)
         (void)hipFree(c->d_tail);
         c->d_tail = nullptr;
         c->tail_cap = 0;
@@ -226,8 +227,10 @@ int end_trace_call(mm_ctx* c, int rc, bool defer, const char* what, uint32_t lau
                    mm_stats* stats) {
     c->last_defer = defer;
     c->calls.end_call(what);
+    // (after a failure too: the launches the call did enqueue are what a call on another stream waits for)
+    const int te = end_timing(c, launches);
     if (rc) return rc;
-    if ((rc = end_timing(c, launches))) return rc;
+    if (te) return te;
     if (want_stats) {
         if ((rc = read_aux(c, stats))) return rc;
         return report_failure(c, "");  // (synced: this call's own error, if any)
@@ -277,13 +280,14 @@ int trace_tile_impl(mm_ctx* c, const mm_uniform* u, const mm_camera* cams, const
     const bool defer = plan.defer, fuse = plan.fuse;
     const uint32_t rows_per_batch = plan.rows_per_batch;
     const uint64_t row_paths = (uint64_t)w * e->spp;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap,
-                                   (size_t)(row_paths * rows_per_batch) * (defer ? n_frames : 1));
+    int rc = fuse ? MM_OK : ensure_idle(c, c->d_samples, c->samples_cap,
+                                        (size_t)(row_paths * rows_per_batch) * (defer ? n_frames : 1));
     if (rc) return rc;
     TailQueue tq;
     if (defer && plan.ring == 1 && (rc = tail_queue(c, tq))) return rc;  // (records in LDS: no global ring)
     const float* cams_dev = nullptr;
     if (cams && (rc = stage_cams(c, cams, n_frames, cams_dev))) return rc;
+    if ((rc = order_shared(c))) return rc;
     if (k.want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
     if ((rc = begin_timing(c))) return rc;
     k.sc = dev_scene(c);
@@ -338,9 +342,10 @@ int list_call(mm_ctx* c, const PlanOptions& opts, const LaunchPlan& plan, const 
     k.want_stats = (e.flags & MM_EXT_COUNT_STATS) != 0;
     if (int rc0 = choose_kernel(c, scene_facts(c), opts, k)) return rc0;
     const bool fuse = plan.fuse;
-    int rc = fuse ? MM_OK : ensure(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e.spp));
+    int rc = fuse ? MM_OK : ensure_idle(c, c->d_samples, c->samples_cap, (size_t)(n_entries * e.spp));
     if (rc) return rc;
     if ((rc = prep(k))) return rc;
+    if ((rc = order_shared(c))) return rc;
     if (k.want_stats) HIPC(c, hipMemsetAsync(c->d_aux, 0, 4 * sizeof(unsigned long long), c->stream));
     if ((rc = begin_timing(c))) return rc;
     k.sc = dev_scene(c);
@@ -521,7 +526,8 @@ int aov_policy(mm_ctx* c, int& policy) {
 // call's status word by a launch of its own).  launch(err_dev) enqueues the kernel.
 template <typename L>
 int enqueue_query_call(mm_ctx* c, const std::string& what, const char* name, L&& launch) {
-    int rc = begin_timing(c);
+    int rc = order_shared(c);
+    if (!rc) rc = begin_timing(c);
     if (rc) return rc;
     c->calls.begin_call();
     rc = enqueue_launch(c, false, [&](uint32_t*, uint32_t) -> int {
@@ -529,8 +535,8 @@ int enqueue_query_call(mm_ctx* c, const std::string& what, const char* name, L&&
         return le == hipSuccess ? MM_OK : fail(c, MM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(le));
     });
     c->calls.end_call(what);
-    if (rc) return rc;
-    return end_timing(c, 2);
+    const int te = end_timing(c, 2);  // (after a failure too, as in end_trace_call)
+    return rc ? rc : te;
 }
 
 }  // namespace
